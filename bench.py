@@ -15,7 +15,12 @@ sharded over the N GPUs -- STRONG scaling (the total work is fixed, every rank h
 predictors by ONE all-to-all by phenotype over RCCL, level 1 phenotype-sharded.  `--weak` keeps the N=1 shape per GPU
 instead (100K SNPs x 50K samples x 1 phenotype per rank: all-gather + shared level 1).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--samples N] [--snps M_per_gpu] [--phenos P] [--weak] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--samples N] [--snps M_per_gpu] [--phenos P] [--weak] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when `--dump-outputs DIR` is given, and prints
+one JSON line.  `--full` adds everything else the line can carry: the per-kernel timing pass and roofline, the device-memory peak,
+the CPU baseline and oracle checks, the run from files on disk and, for the default N=1 workload, the sub-records of the other
+BASELINE configurations (`--oracle-check` and `--disk-leg` imply `--full`).
 """
 from __future__ import annotations
 
@@ -103,7 +108,13 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only for the "
                     "single-box smoke of the N>1 code path")
     ap.add_argument("--single-device", action="store_true", help="test mode: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: per-kernel timing pass and roofline, device-memory peak, CPU baseline "
+                    "and oracle checks, the from-files leg and the sub-records of the default N=1 run (the --no-* switches trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned (LOCO rows, level-1 "
+                    "CV sums, selected ridge index; rank 0's share for N>1) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.oracle_check or args.disk_leg:
+        args.full = True
 
     import torch
     import torch.distributed as dist
@@ -312,8 +323,9 @@ def main():
                 fr, tot = torch.cuda.mem_get_info(dev)
                 self.peak = max(self.peak, tot - fr)
                 time.sleep(0.01)
-    mem = _MemPeak()
-    mem.start()
+    mem = _MemPeak() if args.full else None
+    if mem:
+        mem.start()
     for _ in range(args.warmup):
         step()
     fence()
@@ -328,13 +340,16 @@ def main():
         dt = float(tt.item())
     sec_per_step = dt / args.steps
     value = M * N * P / sec_per_step
-    mem.stop = True
-    mem.join()
-    extra_t["device_memory_peak_GB"] = mem.peak / 1e9      # includes the resident synthetic genotypes and W
+    if mem:
+        mem.stop = True
+        mem.join()
+        extra_t["device_memory_peak_GB"] = mem.peak / 1e9      # includes the resident synthetic genotypes and W
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # ---- per-kernel timing pass (HIP events on the ctx stream) + roofline of the dominant kernel ----
     roof, kernels = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.enable_timing(True)
         step(exchange=False, solo=True)   # rank-0-only pass: no collective may be issued here (W is already gathered)
         tm = eng.timing()
@@ -471,12 +486,12 @@ def main():
             del Wb
         extra_t["level0_vs_oracle"] = {"W_max_rel_err": werr, "blocks": len(osel), "block_order": [blocks[b][2] for b in osel], "samples": N, "phenos": P,
                                        "oracle": "oracle.regenie_step1.ridge_level_0_loocv (eigendecomposition route, Step1_Models.cpp:615-726)", "oracle_s": t_or}
-    elif rank == 0 and world == 1 and (not args.no_cpu or args.oracle_check) and not args.loocv and not args.t2e:
+    elif rank == 0 and world == 1 and args.full and (not args.no_cpu or args.oracle_check) and not args.loocv and not args.t2e:
         cpu = cpu_baseline(args, eng, torch, dev, packed, blocks, my_blocks, X, Y, Yraw, cov, mask, ain, neff, cv_sizes, tau, M, N, P, B, R0,
                            (res[0], res[1], res[2]), with_reference=not (args.no_cpu or args.no_ref))
 
     disk = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.no_disk:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and not args.no_disk:
         disk = from_disk_leg(args, torch, packed, blocks, my_blocks, Yraw, cov, M, N, P, res[0])
     elif rank == 0 and world == 1 and args.disk_leg:      # forced (the configs[2] sub-run of the default line): the device is handed over first
         loco_ck_forced = float(sum(np.abs(l).sum() for l in res[0]))
@@ -494,7 +509,7 @@ def main():
     # ---- sub-records of the default N=1 run (the engine's memory is released first) ----
     extra = {}
     p4 = None
-    default_n1 = rank == 0 and world == 1 and not args.no_cpu and not args.no_extra and (N, M, P) == (50000, 100000, 1)
+    default_n1 = rank == 0 and world == 1 and args.full and not args.no_cpu and not args.no_extra and (N, M, P) == (50000, 100000, 1)
     if default_n1:
         loco_ck = float(sum(np.abs(l).sum() for l in res[0]))
         eng.close()
@@ -503,7 +518,7 @@ def main():
         torch.cuda.empty_cache()
         import subprocess
         me = [sys.executable, os.path.abspath(__file__)]
-        big = ["--samples", "500000", "--steps", "1", "--no-cpu"]
+        big = ["--samples", "500000", "--steps", "1", "--no-cpu", "--full"]
 
         def sub_line(argv, timeout):
             r = subprocess.run(me + argv, capture_output=True, text=True, timeout=timeout)
@@ -765,6 +780,36 @@ def measured_traffic(dom, nblocks, n_batches, P):
 
 def math_sqrt(x):
     return float(np.sqrt(x))
+
+
+DUMP_BUDGET = 64 << 20      # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(d, res):
+    """`--dump-outputs DIR`: what the last timed step returned, as float64 .npy files -- `loco` [P, samples, rows] (the LOCO rows of every
+    trait), `cv_sums` (the level-1 CV statistics), `selected_tau_index` [P].  LOCO rows beyond the budget are cut to a fixed, seeded sample
+    of the samples (the same for every trait, sorted), whose indices go to `loco_sample_index`."""
+    os.makedirs(d, exist_ok=True)
+
+    def f64(a):
+        try:
+            return np.asarray(a, dtype=np.float64)
+        except ValueError:      # ragged per-trait lists (--t2e): concatenated
+            return np.concatenate([np.ravel(np.asarray(x, dtype=np.float64)) for x in a])
+    out = {"selected_tau_index": f64(res[2])}
+    if res[1] is not None:
+        out["cv_sums"] = f64(res[1])
+    n, rows = np.shape(res[0][0])
+    room = DUMP_BUDGET - sum(a.nbytes for a in out.values()) - (64 << 10)      # npy headers
+    if 8 * len(res[0]) * n * rows > room:
+        keep = room // (8 * (len(res[0]) * rows + 1))
+        idx = np.sort(np.random.default_rng(12345).choice(n, size=keep, replace=False))
+        out["loco_sample_index"] = idx.astype(np.float64)
+        out["loco"] = np.stack([np.asarray(l, dtype=np.float64)[idx] for l in res[0]])
+    else:
+        out["loco"] = np.stack([np.asarray(l, dtype=np.float64) for l in res[0]])
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def from_disk_leg(args, torch, packed, blocks, my_blocks, Yraw, cov, M, N, P, gpu_loco, free_gpu=None, nruns=3):

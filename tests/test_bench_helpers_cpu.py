@@ -112,3 +112,26 @@ def test_summary_digest_of_a_recorded_line_fits_the_tail_a_reader_keeps():
     # a line whose sub-runs failed still gets a digest, with the failures named
     s = b.summary_of({"ms_per_step": 30.0, "roofline": {"frac": 0.4}, "config3_single_gpu": {"error": "x"}, "step2": {"error": "y"}})
     assert s["errors_in"] == ["config3_single_gpu", "step2"] and s["cfg2_1gpu"]["ms"] is None
+
+
+def test_dump_outputs_writes_float64_within_the_budget_with_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's returns as float64 .npy files.  A small run is written whole; LOCO rows beyond the
+    64 MB budget are cut to the same seeded sample of the samples on every run, with its indices beside them."""
+    b = _bench()
+    rng = np.random.default_rng(5)
+    loco = [rng.standard_normal((1000, 23))]
+    b.dump_outputs(str(tmp_path / "small"), (loco, rng.standard_normal((1, 5, 5)), np.array([3], np.int32), 1.0))
+    got = {f[:-4]: np.load(str(tmp_path / "small" / f)) for f in os.listdir(str(tmp_path / "small"))}
+    assert set(got) == {"loco", "cv_sums", "selected_tau_index"} and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["loco"][0], loco[0]) and got["selected_tau_index"].tolist() == [3.0]
+    big = np.arange(10 * 23 * 200000, dtype=np.float64).reshape(10, 23, 200000)     # [P][rows][N]: the engine hands out transposed views
+    res = ([big[p].T for p in range(10)], np.ones((10, 5, 5)), np.arange(10, dtype=np.int32))
+    for d in ("big1", "big2"):
+        b.dump_outputs(str(tmp_path / d), res)
+    files = os.listdir(str(tmp_path / "big1"))
+    assert sum(os.path.getsize(str(tmp_path / "big1" / f)) for f in files) <= 64 << 20
+    idx = np.load(str(tmp_path / "big1" / "loco_sample_index.npy")).astype(np.int64)
+    sub = np.load(str(tmp_path / "big1" / "loco.npy"))
+    assert 0 < idx.size < 200000 and np.all(np.diff(idx) > 0) and sub.shape == (10, idx.size, 23)
+    assert np.array_equal(sub, np.stack([big[p].T[idx] for p in range(10)]))
+    assert all(np.array_equal(np.load(str(tmp_path / "big1" / f)), np.load(str(tmp_path / "big2" / f))) for f in files)

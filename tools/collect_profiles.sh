@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=${ROUND:-r1}
 O=gpurun_out/$R
 mkdir -p $O
-python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/${R}_bench_line.json
+python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/${R}_bench_line.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 4 --warmup 1 --no-cpu > $O/stats.log 2>&1
 python tools/prof_summary.py $O/stats $O/${R}_kernel_stats.md > /dev/null
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${R}_kernel_stats.csv

@@ -10,4 +10,4 @@ cp gpurun_out/fin_c3traffic/traffic.json $P/${R}_config3_traffic.json
 RX="k_bt_|k_wgram|k_wsplit|k_wg_reduce|k_bed_prep_rows" OUT=fin_c4traffic bash tools/gpu_job.sh traffic 525 4 --samples 500000 --snps 51200 --bsize 100 --phenos 4 --bt --prev 0.05,0.3,0.01,0.5 --steps 1 --warmup 0 --no-cpu | tail -2
 cp gpurun_out/fin_c4traffic/traffic.json $P/${R}_config4_traffic.json
 timeout 600 python -m pytest tests/test_cli_gpu.py tests/test_step1_gpu.py -q -k "staged or step1" 2>&1 | tail -3
-OUT=fin_bench TMO=1700 bash tools/gpu_job.sh bench
+OUT=fin_bench TMO=1700 bash tools/gpu_job.sh bench --full

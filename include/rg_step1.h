@@ -332,6 +332,30 @@ int rg_k_chol_solve(void* stream, double* mats, int64_t mat_stride, int32_t batc
 int rg_k_dgemm_nt(void* stream, const double* A, int64_t lda, const double* B, int64_t ldb,
                   int32_t m, int32_t n, int64_t k, double* C, int64_t ldc);
 
+/* G~X / G~Y of level 0 over nblk blocks of cleaned 2-bit rows in position space (pk: row r of block b at b * pk_blk_stride +
+ * r * pk_ld, pk_ld a multiple of 16 and >= Np / 4; bs[b] in [1, n128] live rows, n128 a multiple of 128; nmiss[b] > 0 marks a
+ * block with missing calls -- bs and nmiss are HOST arrays).  The folds hold fold_len[f] samples each (HOST array), laid out as
+ * rg_set_problem lays them out: each fold padded to a multiple of 256 positions, Np = the padded total.  V: [Cv][Np] fp64.
+ *   route 0: the digit planes of V (k_v_split), then the i8 matrix-core contraction (k_xy_i8 + k_xy_combine);
+ *            S32 is its workspace, >= nblk * 2 * nseg * n128 * 128 int32;
+ *   route 1: the fp64 kernel of RG_XY_F64=1 (k_geno_xy) over rg_set_problem's chunk table (<= 4096 positions, inside a fold).
+ * part [nblk][nchunk][n128][2][Cv] (0: sum of the allele counts times V, 1: of the missing indicators, written only where
+ * nmiss[b] > 0), nchunk = nseg for route 0 or the number of chunks for route 1, as level 0 reads it; *nchunk_out = nchunk.
+ * part == NULL only reports nchunk.  Synchronises the stream. */
+int rg_k_xy_i8(void* stream, const uint8_t* pk, int64_t pk_ld, int64_t pk_blk_stride, int32_t nblk, int32_t n128,
+               const int32_t* bs, const int32_t* nmiss, int32_t nseg, const int64_t* fold_len, const double* V, int64_t Np,
+               int32_t Cv, int32_t route, int32_t* S32, int64_t s32_elems, double* part, int64_t part_elems,
+               int32_t* nchunk_out);
+/* The weighted Gram of the logistic ridge, sum over a chain's training positions of w_chain(pos) W_r(pos) W_c(pos), for nslot
+ * chains (slot s -> chain slot_chain[s], a HOST array) with tau = 0: out[s] is (n64 + 64) x n64 row-major, n64 = L rounded up to 64,
+ * its lower 64 x 64 tiles as k_wg_reduce leaves them.  W: [L][P][Np] predictor rows (phenotype p), wv: [nchain][Np] weights (0 on
+ * padding positions); fold_len (HOST) gives the fold layout as for rg_k_xy_i8; excl_own: a chain leaves its own fold out (chains are
+ * folds).  fmt 0: fp64 (k_wgram128); 1: fp16 operands, 2: bf16 hi + lo operands (k_wsplit + k_wgram_mx, the quasi-Newton Hessian),
+ * for which *nslice_out = the K slices used (0 for fmt 0).  Synchronises the stream. */
+int rg_k_wgram(void* stream, const double* W, int64_t Np, int32_t L, int32_t P, int32_t p, const double* wv, int32_t nchain,
+               int32_t nseg, const int64_t* fold_len, const int32_t* slot_chain, int32_t nslot, int32_t excl_own, int32_t fmt,
+               double* out, int32_t* nslice_out);
+
 /* register-only MFMA issue-rate micro-benchmark: kind 0 = v_mfma_f64_16x16x4_f64 (TFLOP/s),
  * kind 1 = v_mfma_i32_32x32x32_i8 (TOP/s); the measured ceilings bench.py quotes next to the peaks. */
 int rg_k_mfma_peak(int kind, int iters, double* tera_ops_out);

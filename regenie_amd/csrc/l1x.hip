@@ -1142,8 +1142,10 @@ int bt_solve(BtState& s, const std::vector<int32_t>& act, const std::vector<doub
     double* d_part = (double*)rg_ws(ctx, 14, sizeof(double) * (size_t)MAXSL * na * c.msz);
     if (!d_part) { ctx->err = "weighted Gram: out of device memory"; return RG_ERR_HIP; }
     L1X_HIP(hipStreamSynchronize(st));      // `act` (host) must have reached d_map before the table is built from it
+    // operand format: one fp16 plane and one product per pair (default), or bf16 hi + lo planes and three products (RG_WGRAM_FMT=bf16x3)
+    static const int fmt = (getenv("RG_WGRAM_FMT") && std::string(getenv("RG_WGRAM_FMT")) == "bf16x3") ? RG_WGRAM_BF16X3 : RG_WGRAM_FP16;
     const int ns = rg_launch_wgram_bf16(ctx, st, c.Wv, c.Np, c.L, c.Pv, s.p, c.n64, s.a.wv, s.d_sw, s.nchain, s.d_map, act.data(), na, s.a.kfold,
-                                        d_part, c.msz, MAXSL);
+                                        d_part, c.msz, MAXSL, fmt);
     if (ns <= 0) { ctx->err = "rg_l1_bt: the quasi-Newton Gram (k_wgram_mx) could not be launched"; return RG_ERR_HIP; }
     Wg128 g2{g, ns, na, nullptr, d_part};
     hipLaunchKernelGGL(k_wg_reduce, dim3(c.T * (c.T + 1) / 2, na), dim3(256), 0, st, g2, c.T);
@@ -1929,4 +1931,56 @@ int rg_l1_cox_impl(rg_ctx* ctx, int pheno, int R1, const double* time, const dou
   { const int rce = rg_emit_pred(ctx, st, c.d_pred, nchr, 0, pred_out); if (rce) return rce; }
   L1X_HIP(hipStreamSynchronize(st));
   return RG_OK;
+}
+
+// ---- single-kernel entry point of the weighted Gram (include/rg_step1.h) ---------------------------------------------------------------
+// A context of its own holds the fold layout and the launchers' workspace slots; everything it allocates is freed before returning.
+extern "C" int rg_k_wgram(void* stream, const double* W, int64_t Np, int32_t L, int32_t P, int32_t p, const double* wv, int32_t nchain,
+                          int32_t nseg, const int64_t* fold_len, const int32_t* slot_chain, int32_t nslot, int32_t excl_own, int32_t fmt,
+                          double* out, int32_t* nslice_out) {
+  if (!W || !wv || !fold_len || !slot_chain || !out || L < 1 || P < 1 || p < 0 || p >= P || nchain < 1 || nseg < 1 || nseg > RG_MAX_SEG ||
+      nslot < 1 || nslot > nchain || fmt < 0 || fmt > RG_WGRAM_BF16X3) return RG_ERR_ARG;
+  for (int f = 0; f < nseg; ++f) if (fold_len[f] < 1) return RG_ERR_ARG;
+  for (int s = 0; s < nslot; ++s)
+    if (slot_chain[s] < 0 || slot_chain[s] >= nchain || (excl_own && slot_chain[s] >= nseg)) return RG_ERR_ARG;
+  rg_ctx ctx;
+  ctx.seg = rg_seg_of_lengths(fold_len, nseg);
+  if (Np != ctx.seg.pos_start[nseg - 1] + ctx.seg.plen[nseg - 1]) return RG_ERR_ARG;
+  ctx.Np = Np;
+  hipStream_t st = (hipStream_t)stream;
+  const int n64 = (int)rg_round_up(L, CT), T = n64 / CT;
+  const int64_t msz = (int64_t)(n64 + CT) * n64;
+  const int MAXSL = 16;
+  int32_t* d_map = nullptr;
+  double *d_zero = nullptr, *d_sw = nullptr;
+  int rc = RG_OK, ns = 0;
+  if (hipMalloc(&d_map, sizeof(int32_t) * nslot) != hipSuccess || hipMalloc(&d_zero, sizeof(double) * Np) != hipSuccess ||
+      (fmt != 0 && hipMalloc(&d_sw, sizeof(double) * nchain * Np) != hipSuccess) ||
+      hipMemcpyAsync(d_map, slot_chain, sizeof(int32_t) * nslot, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(d_zero, 0, sizeof(double) * Np, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    rc = RG_ERR_HIP;
+  } else {
+    WgArgs g{W, d_zero, Np, L, P, p, n64, wv, nullptr, nullptr, d_map, excl_own, out, msz};
+    if (fmt == 0) {
+      rc = launch_wgram(&ctx, st, g, T, nslot);
+    } else {
+      double* d_part = (double*)rg_ws(&ctx, 14, sizeof(double) * (size_t)MAXSL * nslot * msz);
+      ns = d_part ? rg_launch_wgram_bf16(&ctx, st, W, Np, L, P, p, n64, wv, d_sw, nchain, d_map, slot_chain, nslot, excl_own, d_part, msz,
+                                         MAXSL, fmt)
+                  : 0;
+      if (ns <= 0) rc = RG_ERR_HIP;
+      else {
+        Wg128 g2{g, ns, nslot, nullptr, d_part};
+        hipLaunchKernelGGL(k_wg_reduce, dim3(T * (T + 1) / 2, nslot), dim3(256), 0, st, g2, T);
+      }
+    }
+    if (hipGetLastError() != hipSuccess) rc = RG_ERR_HIP;
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) rc = RG_ERR_HIP;
+  for (int i = 0; i < 16; ++i) if (ctx.ws_ptr[i]) hipFree(ctx.ws_ptr[i]);
+  if (d_map) hipFree(d_map);
+  if (d_zero) hipFree(d_zero);
+  if (d_sw) hipFree(d_sw);
+  if (nslice_out) *nslice_out = ns;
+  return rc;
 }

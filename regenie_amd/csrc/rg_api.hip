@@ -920,4 +920,51 @@ int rg_k_dgemm_nt(void* stream, const double* A, int64_t lda, const double* B, i
   return hipGetLastError() == hipSuccess ? RG_OK : RG_ERR_HIP;
 }
 
+int rg_k_xy_i8(void* stream, const uint8_t* pk, int64_t pk_ld, int64_t pk_blk_stride, int32_t nblk, int32_t n128, const int32_t* bs,
+               const int32_t* nmiss, int32_t nseg, const int64_t* fold_len, const double* V, int64_t Np, int32_t Cv, int32_t route,
+               int32_t* S32, int64_t s32_elems, double* part, int64_t part_elems, int32_t* nchunk_out) {
+  if (!pk || !bs || !nmiss || !fold_len || !V || nblk < 1 || n128 < 128 || (n128 % 128) || nseg < 1 || nseg > RG_MAX_SEG ||
+      Cv < 1 || (route != 0 && route != 1)) return RG_ERR_ARG;
+  for (int f = 0; f < nseg; ++f) if (fold_len[f] < 1) return RG_ERR_ARG;
+  const SegLayout seg = rg_seg_of_lengths(fold_len, nseg);
+  if (Np != seg.pos_start[nseg - 1] + seg.plen[nseg - 1] || (pk_ld & 15) || pk_ld * 4 < Np ||
+      (nblk > 1 && ((pk_blk_stride & 15) || pk_blk_stride < (int64_t)n128 * pk_ld))) return RG_ERR_ARG;
+  for (int b = 0; b < nblk; ++b) if (bs[b] < 1 || bs[b] > n128 || nmiss[b] < 0) return RG_ERR_ARG;
+  // route 1 writes one partial per position chunk, the table rg_set_problem builds (<= 4096 positions, inside one fold)
+  std::vector<int64_t> cpos, clen;
+  for (int f = 0; f < nseg; ++f)
+    for (int64_t o = 0; o < seg.plen[f]; o += 4096) { cpos.push_back(seg.pos_start[f] + o); clen.push_back(std::min<int64_t>(4096, seg.plen[f] - o)); }
+  const int nchunk = route == 0 ? nseg : (int)cpos.size();
+  if (nchunk_out) *nchunk_out = nchunk;
+  if (!part) return RG_OK;
+  if (part_elems < (int64_t)nblk * nchunk * n128 * 2 * Cv) return RG_ERR_ARG;
+  if (route == 0 && (!S32 || s32_elems < (int64_t)nblk * 2 * nseg * n128 * 128)) return RG_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *d_bs = nullptr, *d_nmiss = nullptr;
+  int8_t* d_vd = nullptr;
+  double* d_vsc = nullptr;
+  int64_t *d_cpos = nullptr, *d_clen = nullptr;
+  bool ok = hipMalloc(&d_bs, sizeof(int32_t) * nblk) == hipSuccess && hipMalloc(&d_nmiss, sizeof(int32_t) * nblk) == hipSuccess &&
+            hipMemcpyAsync(d_bs, bs, sizeof(int32_t) * nblk, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemcpyAsync(d_nmiss, nmiss, sizeof(int32_t) * nblk, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok && route == 0) {
+    ok = hipMalloc(&d_vd, (size_t)Cv * 8 * Np) == hipSuccess && hipMalloc(&d_vsc, sizeof(double) * Cv) == hipSuccess;
+    if (ok) {
+      rg_launch_v_split(st, V, Np, Cv, d_vd, d_vsc);
+      rg_launch_xy_i8(st, pk, pk_ld, pk_blk_stride, d_bs, d_nmiss, nblk, n128, seg, d_vd, d_vsc, Np, Cv, S32, part);
+    }
+  } else if (ok) {
+    ok = hipMalloc(&d_cpos, sizeof(int64_t) * nchunk) == hipSuccess && hipMalloc(&d_clen, sizeof(int64_t) * nchunk) == hipSuccess &&
+         hipMemcpyAsync(d_cpos, cpos.data(), sizeof(int64_t) * nchunk, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(d_clen, clen.data(), sizeof(int64_t) * nchunk, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) rg_launch_geno_xy(st, pk, pk_ld, pk_blk_stride, d_bs, d_nmiss, nblk, n128, V, Np, Cv, d_cpos, d_clen, nchunk, part);
+  }
+  if (ok) ok = hipGetLastError() == hipSuccess;
+  // the host tables and the temporaries must outlive the launches
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  for (void* q : {(void*)d_bs, (void*)d_nmiss, (void*)d_vd, (void*)d_vsc, (void*)d_cpos, (void*)d_clen})
+    if (q) hipFree(q);
+  return ok ? RG_OK : RG_ERR_HIP;
+}
+
 }  // extern "C"

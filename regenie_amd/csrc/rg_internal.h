@@ -39,6 +39,22 @@ struct SegLayout {
   int64_t plen[RG_MAX_SEG];     // padded length (multiple of 256)
 };
 
+// the layout rg_set_problem builds for folds of `len[f]` samples in file order with none ignored (the single-kernel test entries)
+static inline SegLayout rg_seg_of_lengths(const int64_t* len, int nseg) {
+  SegLayout sg{};
+  sg.nseg = nseg;
+  int64_t pos = 0, file = 0;
+  for (int f = 0; f < nseg; ++f) {
+    sg.file_start[f] = file;
+    sg.len[f] = len[f];
+    sg.plen[f] = rg_round_up(len[f], 256);
+    sg.pos_start[f] = pos;
+    pos += sg.plen[f];
+    file += len[f];
+  }
+  return sg;
+}
+
 struct rg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -334,9 +350,11 @@ struct L1Args;
 int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_t* cols_per_chr,
                   double* cumsum_out, int32_t* best_out, double* pred_out);
 // wgram_bf16.hip: partial tiles of the quasi-Newton weighted Gram (one fp16 operand plane, or bf16 hi + lo planes, on the matrix cores); returns the K slices written (0 = failed)
+#define RG_WGRAM_FP16 1     // operand formats of rg_launch_wgram_bf16: one fp16 plane, one product per pair
+#define RG_WGRAM_BF16X3 2   //                                          bf16 hi + lo planes, three products per pair
 int rg_launch_wgram_bf16(rg_ctx* ctx, hipStream_t st, const double* W, int64_t Np, int L, int P, int p, int n64, const double* wv, double* sw, int nchain,
                          const int32_t* d_chainmap, const int32_t* h_chainmap, int nslot, int excl_own, double* part, int64_t out_stride,
-                         int max_slices);
+                         int max_slices, int fmt);
 // l1x.hip
 int rg_l1_qt_loocv_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_t* cols_per_chr,
                         double* cumsum_out, int32_t* best_out, double* pred_out);

@@ -35,7 +35,6 @@
 //   k_wg_reduce    (l1x.hip) sums the K slices in a fixed order and puts tau on the diagonal
 #include <algorithm>
 #include <cstdlib>
-#include <string>
 #include <vector>
 #include "rg_internal.h"
 
@@ -267,10 +266,11 @@ __global__ __launch_bounds__(1024) void k_wgram_mx(WbArgs g, SegLayout seg) {
 // wv: [nchain][Np] weights, sw: scratch of the same size for their square roots; V / items live in workspace slots 15 / 13 of the context.
 int rg_launch_wgram_bf16(rg_ctx* ctx, hipStream_t st, const double* W, int64_t Np, int L, int P, int p, int n64, const double* wv, double* sw, int nchain,
                          const int32_t* d_chainmap, const int32_t* h_chainmap, int nslot, int excl_own, double* part, int64_t out_stride,
-                         int max_slices) {
+                         int max_slices, int fmt) {
   const SegLayout& seg = ctx->seg;
-  // operand format: one fp16 plane and one product per pair (default), or bf16 hi + lo planes and three products (RG_WGRAM_FMT=bf16x3)
-  static const bool F16 = !(getenv("RG_WGRAM_FMT") && std::string(getenv("RG_WGRAM_FMT")) == "bf16x3");
+  // operand format: one fp16 plane and one product per pair (RG_WGRAM_FP16), or bf16 hi + lo planes and three products (RG_WGRAM_BF16X3)
+  if (fmt != RG_WGRAM_FP16 && fmt != RG_WGRAM_BF16X3) return 0;
+  const bool F16 = fmt == RG_WGRAM_FP16;
   const int WB_CHUNK = F16 ? WbFmt<true>::CHUNK : WbFmt<false>::CHUNK, WB_FLUSH = F16 ? WbFmt<true>::FLUSH : WbFmt<false>::FLUSH;
   const int64_t all = seg.pos_start[seg.nseg - 1] + seg.plen[seg.nseg - 1];
   int64_t min_vs = all / WB_CHUNK;

@@ -16,8 +16,9 @@ def gpu_step1(opt: orc.Step1Options, nblk_env=None):
     bed, bpr = orc.open_bed(opt.bed + ".bed", prep.n_file)
     blocks = orc.chrom_blocks(chrom, bim.chr_read, opt.bsize)
     B = len(blocks)
-    h0 = orc.set_ridge_params(opt.n_ridge_l0)
-    h1 = orc.set_ridge_params(opt.n_ridge_l1)
+    # --l0 / --l1 values given explicitly (setl0 / setl1) or as a count, as orc.run_step1 takes them
+    h0 = np.unique(np.asarray(opt.setl0, np.float64)) if opt.setl0 is not None else orc.set_ridge_params(opt.n_ridge_l0)
+    h1 = np.unique(np.asarray(opt.setl1, np.float64)) if opt.setl1 is not None else orc.set_ridge_params(opt.n_ridge_l1)
     M = chrom.size
     lam = M * (1 - h0) / h0
     cv_sizes = orc.set_folds(prep.ind_in_analysis, opt.cv_folds)

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void k_bed_prep_rows(const uint8_t* const* __r
   // aligned dwords around it (a dword that holds at least one valid byte never crosses into an unmapped page)
   const uint8_t* rowp = rawptr[blk] + (int64_t)min(row, bs - 1) * raw_ld;   // padding rows (>= bs) read nothing new
   uint32_t* po = reinterpret_cast<uint32_t*>(pk + (int64_t)blk * pk_blk_stride + (int64_t)row * pk_ld);
-  uint2* p4 = pk4 ? reinterpret_cast<uint2*>(pk4 + (int64_t)blk * pk4_blk_stride + (int64_t)row * pk4_ld) : nullptr;
+  uint2* p4 = reinterpret_cast<uint2*>(pk4 + (int64_t)blk * pk4_blk_stride + (int64_t)row * pk4_ld);
   const uint4* a128 = reinterpret_cast<const uint4*>(act);
   int nmiss = 0, gsum = 0;
   // A thread handles GROUPS of 64 positions (4 output dwords: one 16-byte store, two for the FP4 plane, one 16-byte load
@@ -109,21 +109,19 @@ __global__ __launch_bounds__(256) void k_bed_prep_rows(const uint8_t* const* __r
         outw[d] = out;
       }
       reinterpret_cast<uint4*>(po)[gq] = make_uint4(outw[0], outw[1], outw[2], outw[3]);
-      if (p4) {
-        // FP4 E2M1 plane for the matrix cores (gram_fp4.hip): dosage 2 (code 00) -> 0100, 1 (code 10) -> 0010,
-        // 0 / missing -> 0000; sample i of a dword -> nibble i of its 8 output bytes
-        unsigned o8[8];
+      // FP4 E2M1 plane for the matrix cores (gram_fp4.hip): dosage 2 (code 00) -> 0100, 1 (code 10) -> 0010,
+      // 0 / missing -> 0000; sample i of a dword -> nibble i of its 8 output bytes
+      unsigned o8[8];
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          const unsigned lo = outw[d] & 0x55555555u, hi = (outw[d] >> 1) & 0x55555555u;
-          const unsigned two = ~lo & ~hi & 0x55555555u, one = ~lo & hi;
-          o8[2 * d] = (spread8(two) << 2) | (spread8(one) << 1);
-          o8[2 * d + 1] = (spread8(two >> 16) << 2) | (spread8(one >> 16) << 1);
-        }
-        uint4* q4 = reinterpret_cast<uint4*>(p4) + 2 * gq;
-        q4[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
-        q4[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
+      for (int d = 0; d < 4; ++d) {
+        const unsigned lo = outw[d] & 0x55555555u, hi = (outw[d] >> 1) & 0x55555555u;
+        const unsigned two = ~lo & ~hi & 0x55555555u, one = ~lo & hi;
+        o8[2 * d] = (spread8(two) << 2) | (spread8(one) << 1);
+        o8[2 * d + 1] = (spread8(two >> 16) << 2) | (spread8(one >> 16) << 1);
       }
+      uint4* q4 = reinterpret_cast<uint4*>(p4) + 2 * gq;
+      q4[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
+      q4[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
     }
   }
   for (int o = 32; o > 0; o >>= 1) {

@@ -31,7 +31,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -325,7 +324,6 @@ __device__ __forceinline__ void emit_match(WaveLds& L, OutState& o, uint32_t len
   }
 }
 
-template <bool PAR>
 __global__ __launch_bounds__(64 * WPB) void k_bgen_inflate(InflateArgs a) {
   __shared__ WaveLds lds[WPB];
   // every quantity of the decode loop is the same in all 64 lanes; uni() (v_readfirstlane) tells the compiler so, and the state then lives in
@@ -416,7 +414,7 @@ __global__ __launch_bounds__(64 * WPB) void k_bgen_inflate(InflateArgs a) {
       if (!build_table(L, 32, (int)hlit, LIT_TB, L.lit, LIT_SLOTS, 0) || !build_table(L, 32 + (int)hlit, (int)hdist, DIST_TB, L.dist, DIST_SLOTS, 1)) { st = ST_TABLE; break; }
     }
     // ---- the block's symbols ----
-    if (PAR) {
+    {
       // Window decoder (round 5): the serial loop below issues ~120 scalar instructions and two or three dependent LDS round trips per
       // symbol (~1 us).  Here all 64 lanes decode SPECULATIVELY the symbol that would start at each of the next 64 bit positions (lane i:
       // bits bp + i ...: literal / length code, extra bits, distance code, extra bits -- at most 48 bits, out of three dwords of the
@@ -832,9 +830,7 @@ int rg_bgen_dev_decode(rg_bgen_dev* h, int32_t slot, int32_t nvar, const uint8_t
   BD_HIP(hipMemcpyAsync(d_ulen, ulen, sizeof(int32_t) * nvar, hipMemcpyHostToDevice, st));
   BD_HIP(hipMemsetAsync(s.d_sums, 0, sums_bytes, st));
   InflateArgs ia{s.d_comp, d_off, d_clen, d_ulen, s.d_raw, stride, d_status, nvar};
-  static const bool serial = getenv("RG_BGEN_SERIAL") != nullptr;      // the one-symbol-at-a-time decoder (kept as the cross-check of the window decoder)
-  if (serial) hipLaunchKernelGGL(k_bgen_inflate<false>, dim3((unsigned)((nvar + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, ia);
-  else hipLaunchKernelGGL(k_bgen_inflate<true>, dim3((unsigned)((nvar + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, ia);
+  hipLaunchKernelGGL(k_bgen_inflate, dim3((unsigned)((nvar + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, ia);
   CheckArgs ca{s.d_comp, d_off, d_clen, d_ulen, s.d_raw, stride, h->n_file, d_status, nvar};
   unsigned long long* d_adler = (unsigned long long*)((uint8_t*)s.d_sums + ((nsum * 8 + (size_t)nvar * 4 + 7) / 8) * 8);
   hipLaunchKernelGGL(k_bgen_adler, dim3(ADLER_SEG, (unsigned)nvar), dim3(256), 0, st, ca, d_adler);

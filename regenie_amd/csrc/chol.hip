@@ -200,9 +200,8 @@ __global__ __launch_bounds__(256, 2) void k_dgemm_nt128(Gemm128 g) {
 
 void rg_launch_dgemm_nt(hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
                         int m, int n, int64_t k, double* C, int64_t ldc) {
-  static const bool old = getenv("RG_DGEMM_REG") != nullptr;
   const bool al = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && lda % 2 == 0 && ldb % 2 == 0;
-  if (old || !al || k % 16 != 0 || (int64_t)m * n < 128 * 128) {
+  if (!al || k % 16 != 0 || (int64_t)m * n < 128 * 128) {
     hipLaunchKernelGGL(k_dgemm_nt, dim3(n / CT, m / CT), dim3(256), 0, st, A, lda, B, ldb, k, C, ldc);
     return;
   }
@@ -1494,13 +1493,12 @@ void rg_launch_chol_solve_src(hipStream_t st, double* mats, int64_t mat_stride, 
   const int row_end = n64 + (nrhs > 0 ? nrhs : rhs_pad);
   double* dimg = dinv + chol_ws_img_offset((size_t)batch, n64);   // the workspace holds the tile inverses, then the images
   FormSrc first = src ? *src : off;
-  first.skip_pad = (src && src->d_n && !getenv("RG_CHOL_FULLPAD")) ? 1 : 0;
+  first.skip_pad = (src && src->d_n) ? 1 : 0;
   FormSrc later = first;          // launches past a tile's first touch: workspace values, but still the per-system orders
   later.enabled = 0;
   // round 6: panels of 128 columns, one launch per panel (chol_p128.h) -- whenever the right-hand sides are embedded (or absent), the order
-  // is a multiple of 128 and every tile is formed from the sources; RG_CHOL_GROUP4=1 keeps the group-of-four kernels below
-  static const bool group4 = getenv("RG_CHOL_GROUP4") && atoi(getenv("RG_CHOL_GROUP4")) != 0;
-  const bool p128 = !group4 && src && src->enabled && !src->extra && Ttot == T && n64 % 128 == 0;
+  // is a multiple of 128 and every tile is formed from the sources; the group-of-four kernels below take every other system
+  const bool p128 = src && src->enabled && !src->extra && Ttot == T && n64 % 128 == 0;
   if (p128) c128_launch_factor(st, mats, mat_stride, batch, n64, dinv, dimg, info, first, R, nl);
   for (int k0 = 0; k0 < T && !p128; k0 += 4) {
     const int nc = std::min(4, T - k0), k1 = k0 + nc;
@@ -1522,9 +1520,8 @@ void rg_launch_chol_solve_src(hipStream_t st, double* mats, int64_t mat_stride, 
   }
   if (nrhs > 0) {
     // several right-hand sides and at most 16 tile rows: one pass over L on the matrix cores; else the VALU kernel (a single right-hand
-    // side is bound by reading L either way).  RG_BACKSOLVE_VALU=1 keeps the VALU kernel.
-    static const bool valu = getenv("RG_BACKSOLVE_VALU") && atoi(getenv("RG_BACKSOLVE_VALU")) != 0;
-    if (nrhs >= 2 && T <= 16 && !valu)
+    // side is bound by reading L either way).
+    if (nrhs >= 2 && T <= 16)
       hipLaunchKernelGGL(k_chol_backsolve_mfma, dim3(batch), dim3(256), 0, st, mats, mat_stride, n64, nrhs, n64, dinv, later);
     else
       hipLaunchKernelGGL(k_chol_backsolve, dim3(batch), dim3(256), 0, st, mats, mat_stride, n64, nrhs, dinv, later);

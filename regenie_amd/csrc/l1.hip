@@ -455,21 +455,15 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
   const int b0 = multi ? (int)((int64_t)nsys * rank / world) : 0;
   const int b1 = multi ? (int)((int64_t)nsys * (rank + 1) / world) : nsys;
   const int nloc = b1 - b0;
-  // Gram work items: tiles (lower triangle + the y row tile) x K slices
+  // 64 x 64 tiles of a fold matrix (lower triangle + the y row tile): the multi-GPU exchange packs them
   const int ntile = T * (T + 1) / 2 + T;
   int64_t min_nch = INT64_MAX;
   for (int f = 0; f < K; ++f) min_nch = std::min(min_nch, ctx->seg.plen[f] / 64);
-  int nslice = (int)std::min<int64_t>(16, std::max<int64_t>(1, (4096 + (int64_t)ntile * K - 1) / ((int64_t)ntile * K)));
-  nslice = (int)std::max<int64_t>(1, std::min<int64_t>(nslice, min_nch / 4));
   // LDS-staged Gram (k_l1_gram128): 128 x 128 macro tiles; K slices until the table holds several rounds of the chip's 512
-  // workgroup slots (equal-cost items: the tail of the last round is what the slices even out).  RG_L1_GRAM64=1 keeps the
-  // register-fed kernel (one wave per 64 x 64 tile).
-  static const bool gram64 = getenv("RG_L1_GRAM64") && atoi(getenv("RG_L1_GRAM64")) != 0;
+  // workgroup slots (equal-cost items: the tail of the last round is what the slices even out).
   const int T2 = (n64 + 127) / 128, ntile2 = T2 * (T2 + 1) / 2;
-  if (!gram64) {
-    nslice = (int)std::min<int64_t>(16, std::max<int64_t>(1, (3072 + (int64_t)ntile2 * K - 1) / ((int64_t)ntile2 * K)));
-    nslice = (int)std::max<int64_t>(1, std::min<int64_t>(nslice, min_nch / 2));      // >= 8 stages of 16 positions per slice
-  }
+  int nslice = (int)std::min<int64_t>(16, std::max<int64_t>(1, (3072 + (int64_t)ntile2 * K - 1) / ((int64_t)ntile2 * K)));
+  nslice = (int)std::max<int64_t>(1, std::min<int64_t>(nslice, min_nch / 2));      // >= 8 stages of 16 positions per slice
 
   double *d_fold = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_wk = nullptr, *d_dinv = nullptr, *d_tau = nullptr,
          *d_cvp = nullptr, *d_pred = nullptr, *d_alpha = nullptr, *d_pack = nullptr;
@@ -489,13 +483,10 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
   L1_WS(d_col0, 9, int32_t, nchr + 1)
   if (multi) { L1_WS(d_pack, 10, double, (size_t)ntile * K * CT * CT) }
   L1Item* d_items = nullptr;
-  std::vector<L1Item> items;
-  if (!gram64) {
-    items = l1_build_items(n64, K, nslice, multi ? world : 1, multi ? rank : 0);
-    L1_WS(d_items, 12, L1Item, items.size())
-    RG_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(L1Item) * items.size(), hipMemcpyHostToDevice, st));
-    RG_HIP(hipStreamSynchronize(st));     // `items` is pageable host memory
-  }
+  const std::vector<L1Item> items = l1_build_items(n64, K, nslice, multi ? world : 1, multi ? rank : 0);
+  L1_WS(d_items, 12, L1Item, items.size())
+  RG_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(L1Item) * items.size(), hipMemcpyHostToDevice, st));
+  RG_HIP(hipStreamSynchronize(st));     // `items` is pageable host memory
 #undef L1_WS
   RG_HIP(hipMemcpyAsync(d_col0, col0.data(), sizeof(int32_t) * (nchr + 1), hipMemcpyHostToDevice, st));
   std::vector<double> hpart((size_t)nch * NPART);
@@ -515,18 +506,12 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
     // ---- fold Grams X_f = W_f^T W_f with W_f^T y_f as an extra row ------------------------------------------
     double* gout = nslice > 1 ? d_part : d_fold;
     hipMemsetAsync(gout, 0, sizeof(double) * msz * K * nslice, st);
-    if (gram64) {
-      L1G64 g{R, T, rtot, nslice, ntile, multi ? world : 1, multi ? rank : 0, gout, msz * K};
-      hipLaunchKernelGGL(k_l1_gram64, dim3((ntile * nslice + 3) / 4, K), dim3(256), 0, st, g, ctx->seg);
-    } else {
-      L1G128 g{R, rtot, nslice, d_items, gout, msz * K};
-      hipLaunchKernelGGL(k_l1_gram128, dim3((unsigned)items.size()), dim3(256), 0, st, g, ctx->seg);
-    }
+    L1G128 g{R, rtot, nslice, d_items, gout, msz * K};
+    hipLaunchKernelGGL(k_l1_gram128, dim3((unsigned)items.size()), dim3(256), 0, st, g, ctx->seg);
     if (nslice > 1)
       hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((msz * K + 255) / 256)), dim3(256), 0, st, d_part, msz * K,
                          nslice, msz * K, d_fold);
-    if (!gram64)
-      hipLaunchKernelGGL(k_l1_wty, dim3(L, K), dim3(256), 0, st, R, ctx->seg, rtot, multi ? world : 1, multi ? rank : 0, d_fold);
+    hipLaunchKernelGGL(k_l1_wty, dim3(L, K), dim3(256), 0, st, R, ctx->seg, rtot, multi ? world : 1, multi ? rank : 0, d_fold);
     if (multi) {  // every rank needs every fold matrix: sum of disjoint tile sets, exchanged tile-packed
       hipLaunchKernelGGL(k_tiles_pack, dim3(ntile, K), dim3(256), 0, st, d_fold, msz, T, n64, d_pack, 0);
       RG_HIP(hipStreamSynchronize(st));

@@ -267,8 +267,7 @@ __global__ __launch_bounds__(256) void k_wg_wz(WgArgs a, SegLayout seg) {
 
 // the weighted Gram of `nslot` chains: LDS-staged form when weights are given (the logistic / Poisson ridge), else the register-fed kernel
 static int launch_wgram(rg_ctx* ctx, hipStream_t st, const WgArgs& a, int T, int nslot) {
-  static const bool old = getenv("RG_WGRAM64") && atoi(getenv("RG_WGRAM64")) != 0;
-  if (!a.wv || old) {
+  if (!a.wv) {
     hipLaunchKernelGGL(k_wgram, dim3((T * (T + 1) / 2 + T + 3) / 4, nslot), dim3(256), 0, st, a, ctx->seg, T);
     return RG_OK;
   }
@@ -1097,8 +1096,7 @@ int bt_chord(BtState& s, const std::vector<int32_t>& act) {
   const size_t lds = tri_solve_lds(c.n64);
   if (lds > 48 * 1024) L1X_HIP(hipFuncSetAttribute((const void*)k_tri_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   double* d_x = s.d_sys;      // [nchain][n64] scratch: the systems' workspace is idle during a chord step
-  static const bool one_wg = getenv("RG_TRI_ONE_WG") && atoi(getenv("RG_TRI_ONE_WG")) != 0;      // the round-4 kernel: one workgroup per system
-  if (one_wg || c.L < 256)
+  if (c.L < 256)      // the round-4 kernel, one workgroup per system; larger systems: one launch per tile row
     hipLaunchKernelGGL(k_tri_solve, dim3(na), dim3(TS_NT), lds, st, (const double*)s.d_fac, c.msz, (const int32_t*)s.d_map, c.n64, c.L, (const double*)s.d_score, d_x);
   else
     launch_tri_rows(st, s.d_fac, c.msz, s.d_map, na, c.n64, c.L, s.d_score, d_x);

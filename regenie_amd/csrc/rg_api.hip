@@ -291,12 +291,8 @@ int rg_set_problem(rg_ctx* ctx, const rg_problem* p) {
   const size_t msz = (size_t)rtot * n64;
   if (ctx->d_raw) { hipFree(ctx->d_raw); ctx->d_raw = nullptr; }   // staging of host rows: allocated by the first RG_MEM_HOST batch
   if ((rc = dev_alloc(ctx, &ctx->d_pk, (size_t)nb * n128 * ctx->pk_ld + 16))) return rc;
-  ctx->gram_fp4 = true;
-  if (const char* e = getenv("RG_GRAM")) ctx->gram_fp4 = std::string(e) != "i8";
   ctx->pk4_ld = Np / 2;
-  if (ctx->gram_fp4) {
-    if ((rc = dev_alloc(ctx, &ctx->d_pk4, (size_t)nb * n128 * ctx->pk4_ld + 16))) return rc;
-  } else if (ctx->d_pk4) { hipFree(ctx->d_pk4); ctx->d_pk4 = nullptr; }
+  if ((rc = dev_alloc(ctx, &ctx->d_pk4, (size_t)nb * n128 * ctx->pk4_ld + 16))) return rc;
   if ((rc = dev_alloc(ctx, &ctx->d_mu, (size_t)nb * n128 * 2))) return rc;  // mu + int scratch
   if ((rc = dev_alloc(ctx, &ctx->d_nmiss, (size_t)nb))) return rc;
   if ((rc = dev_alloc(ctx, &ctx->d_xypart, (size_t)nb * ctx->xy_nchunk * n128 * 2 * Cv))) return rc;
@@ -472,7 +468,7 @@ static int l0_batch(rg_ctx* ctx, int nblk, const int32_t* block_ids, const int32
     RG_HIP(hipMemcpyAsync(ctx->d_rawptr, hp.data(), sizeof(uint8_t*) * nblk, hipMemcpyHostToDevice, st));
     rg_launch_bed_prep(st, ctx->d_rawptr, ld, ctx->d_pk, ctx->pk_ld, pk_blk, ctx->d_bs,
                        nblk, n128, ctx->d_act, ctx->seg, ctx->Np, ctx->ref_first, ctx->n_active,
-                       ctx->d_mu, ctx->d_nmiss, ctx->gram_fp4 ? ctx->d_pk4 : nullptr, ctx->pk4_ld,
+                       ctx->d_mu, ctx->d_nmiss, ctx->d_pk4, ctx->pk4_ld,
                        (int64_t)n128 * ctx->pk4_ld);
   }
   {
@@ -486,10 +482,8 @@ static int l0_batch(rg_ctx* ctx, int nblk, const int32_t* block_ids, const int32
   }
   {
     StageTimer t(ctx, &ctx->tm.ms_gram);
-    if (ctx->gram_fp4)
-      rg_launch_gram_fp4_blocks(st, ctx->d_pk4, ctx->pk4_ld, (int64_t)n128 * ctx->pk4_ld, nblk, n128, ctx->seg, ctx->d_S);
-    rg_launch_gram_blocks(st, ctx->d_pk, ctx->pk_ld, pk_blk, nblk, n128, ctx->seg, ctx->d_nmiss, ctx->d_S,
-                          ctx->gram_fp4 ? 1 : 0);
+    rg_launch_gram_fp4_blocks(st, ctx->d_pk4, ctx->pk4_ld, (int64_t)n128 * ctx->pk4_ld, nblk, n128, ctx->seg, ctx->d_S);
+    rg_launch_gram_blocks(st, ctx->d_pk, ctx->pk_ld, pk_blk, nblk, n128, ctx->seg, ctx->d_nmiss, ctx->d_S);
     ctx->tm.n_gram_launches += 1;
   }
   // K-fold level 0 with room in the padding rows of the blocks' last tiles: the right-hand sides are embedded in the systems
@@ -612,12 +606,7 @@ int rg_l0_blocks(rg_ctx* ctx, int32_t nblk, const int32_t* block_ids, const int3
   // driver streaming one batch per call from a reader thread) keep alternating pipelines and overlap, exactly like the
   // batches of one big call.  The per-stage timing mode keeps a single pipeline so that its HIP-event brackets stay meaningful.
   const int npipe = (ctx->twin && !ctx->timing) ? ctx->n_pipe : 1;
-  int nbatch = (nblk + ctx->nblk_cap - 1) / ctx->nblk_cap;
-  {
-    // RG_BATCH_ROUND=1 rounds the number of batches of a call up to a multiple of the pipelines
-    static const bool round_up = getenv("RG_BATCH_ROUND") && atoi(getenv("RG_BATCH_ROUND")) != 0;
-    if (npipe > 1 && nblk >= 2 * npipe && round_up) nbatch = (nbatch + npipe - 1) / npipe * npipe;
-  }
+  const int nbatch = (nblk + ctx->nblk_cap - 1) / ctx->nblk_cap;
   const int per = (nblk + nbatch - 1) / nbatch;
   const bool multi = npipe > 1;
   if (multi && !ctx->join_pending) {

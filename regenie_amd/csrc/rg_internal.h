@@ -110,7 +110,6 @@ struct rg_ctx {
   uint8_t* d_raw = nullptr;  int64_t raw_ld = 0;    // staged raw rows [nblk][bs_max][raw_ld]
   uint8_t* d_pk = nullptr;   int64_t pk_ld = 0;     // cleaned packed   [nblk][n128][pk_ld]
   uint8_t* d_pk4 = nullptr;  int64_t pk4_ld = 0;    // FP4 dosage plane [nblk][n128][pk4_ld] (gram_fp4.hip)
-  bool gram_fp4 = true;          // dosage x dosage Gram on the FP4 matrix cores (RG_GRAM=i8 selects the i8 kernel)
   double* d_mu = nullptr;        // [nblk][n128]
   int32_t* d_nmiss = nullptr;    // [nblk]
   double* d_xypart = nullptr;    // [nblk][nchunk][n128][2][Cv]
@@ -252,7 +251,7 @@ void rg_launch_geno_xy(hipStream_t st, const uint8_t* pk, int64_t pk_ld, int64_t
                        int Cv, const int64_t* chunk_pos, const int64_t* chunk_len, int nchunk, double* part);
 // gram_i8.hip
 void rg_launch_gram_blocks(hipStream_t st, const uint8_t* pk, int64_t pk_ld, int64_t pk_blk_stride,
-                           int nblk, int n128, SegLayout seg, const int32_t* nmiss, int32_t* S, int miss_only);
+                           int nblk, int n128, SegLayout seg, const int32_t* nmiss, int32_t* S);
 // gram_fp4.hip
 void rg_launch_gram_fp4_blocks(hipStream_t st, const uint8_t* pk4, int64_t pk4_ld, int64_t pk4_blk_stride, int nblk,
                                int n128, SegLayout seg, int32_t* S);

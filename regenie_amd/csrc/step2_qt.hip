@@ -1552,8 +1552,7 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
     double* beta = (double*)ctx->buf[B_BETA];
     corr = (double*)ctx->buf[B_CORR];
     hipLaunchKernelGGL(k_s2_beta_from_sums, dim3((bs * C + 255) / 256), dim3(256), 0, ctx->st, (const double*)A, (const double*)vstat, inv_scale, bs, C, Cv, beta);
-    static const bool per_variant = getenv("RG_S2_MASKED_OLD") && atoi(getenv("RG_S2_MASKED_OLD")) != 0;
-    if (per_variant || C > 32)      // the matrix-core form carries two column tiles
+    if (C > 32)      // the matrix-core form carries two column tiles
       hipLaunchKernelGGL(k_s2_masked_int, dim3(bs, P), dim3(256), 0, ctx->st, dG, ldg, inv_scale, (const double*)ctx->d_xl, C, ctx->d_mlist, ctx->d_moff,
                          (const double*)vstat, (const double*)beta, P, corr);
     else

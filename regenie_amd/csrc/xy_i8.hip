@@ -15,7 +15,6 @@
 // idiom of gram_i8.hip).  At 500,000 samples and 13 columns this is 1.3*10^11 integer multiply-adds per block against the
 // 29 ms per 32 blocks of the fp64 VALU kernel.
 #include "rg_internal.h"
-#include <cstdlib>
 
 #define XT 128
 #define X_PITCH 80
@@ -604,11 +603,10 @@ void rg_launch_v_split(hipStream_t st, const double* V, int64_t Np, int Cv, int8
 // are neither loaded nor multiplied): S32 [ngrp][2][nseg][n128][128]; lut0 = what set 0 contracts (the allele count, or its square); set 1 is the missing
 // indicator, skipped when *nmiss == 0
 // Two column groups whose second holds at most 32 (column, digit) pairs -- 17 to 20 columns -- go in ONE pass (k_xy_i8_*_x): the caller sizes its segments for that
-// many groups of workgroups (RG_XY_NO_FUSE=1: always one pass per group).
+// many groups of workgroups.
 int rg_xy_i8_launch_groups(int ncols) {
-  static const bool no_fuse = getenv("RG_XY_NO_FUSE") && atoi(getenv("RG_XY_NO_FUSE")) != 0;
   const int ngrp = (ncols + 15) / 16;
-  return (!no_fuse && ngrp == 2 && (ncols - 16) * X_NPIECE <= 32) ? 1 : ngrp;      // (E = 2, up to 24 columns: the both-sets kernel spills at 256 registers)
+  return (ngrp == 2 && (ncols - 16) * X_NPIECE <= 32) ? 1 : ngrp;      // (E = 2, up to 24 columns: the both-sets kernel spills at 256 registers)
 }
 void rg_launch_xy_i8_sums(hipStream_t st, const uint8_t* pk, int64_t pk_ld, const int32_t* d_bs, const int32_t* nmiss, int ncols, int n128,
                           const SegLayout& seg, const int8_t* vd, int64_t Np, unsigned lut0, int32_t* S32) {

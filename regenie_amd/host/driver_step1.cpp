@@ -953,8 +953,7 @@ int run(int argc, char** argv) {
 
   auto tl0 = std::chrono::steady_clock::now();
   if (!use_group) {
-    const bool l1_batched = getenv("RG_L1_BATCHED") && atoi(getenv("RG_L1_BATCHED")) != 0;
-    if (!l1_batched) l1_slots_start();
+    l1_slots_start();
     if (!p.run_l1) {
       std::ostringstream lg;
       level0_range(ctx, 0, B, lg, pre_ring_ptr);
@@ -964,8 +963,7 @@ int run(int argc, char** argv) {
     if (p.ct) sout << " Level 1 ridge with poisson regression...\n";
     if (p.t2e) sout << " Level 1 ridge with cox regression...\n";
     tl0 = std::chrono::steady_clock::now();
-    if (l1_batched) level1_range(ctx, 0, P, true);   // all phenotypes in one call, then the files
-    else level1_pipelined(ctx);
+    level1_pipelined(ctx);
   } else {
     // one host thread per GPU: level 0 of the rank's blocks, the exchange, level 1 of the rank's phenotypes (phenotype-
     // sharded) or of all phenotypes with the heavy steps shared (all-gather form; level-1 models other than the K-fold

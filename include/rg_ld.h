@@ -1,0 +1,76 @@
+/* rg_ld.h -- C ABI of the Step-2 LD matrix of a region (`regenie --step 2 --compute-corr`, hard calls).
+ *
+ * What it replaces in the reference: Data::print_ld (Data.cpp:4368-4449) and the sparse matrix get_G_svs fills for it
+ * (Data.cpp:4227-4304): for M variants and n analysed samples
+ *     LD = G^T G - (G^T X)(G^T X)^T        G [n][M] hard calls, every variant mean-imputed (mean_impute_g, Data.cpp:4278-4279),
+ *                                          X [n][C] the orthonormal covariate basis (new_cov, intercept included)
+ * then the reference's treatment of the diagonal and the scaling to correlations (Data.cpp:4386-4397), and the 16-bit R^2
+ * quantisation of the binary file (Data.cpp:4431-4436).
+ *
+ * How: with g0 = the call with 0 at a missing entry, miss = its indicator and m_j the mean of the observed calls of variant j,
+ *     sum_s g_i g_j = A_ij + m_j B_ij + m_i B_ji + m_i m_j D_ij,    A = g0 g0^T,  B_ij = sum_s g0_i miss_j,  D = miss miss^T
+ * A, B, D are integers, computed exactly on the i8 matrix cores from the 2-bit rows (int32 sums: n < 2^29); B and D only for tile
+ * pairs in which a tile has a missing call.  X^T g comes from the contraction primitive of rg_step2.h (exact digit planes).  The
+ * combination, the subtraction, the scaling and the quantisation are fp64 on the vector units (csrc/ld_corr.hip).
+ *
+ * Layout: rows are 2-bit hard calls in .bed coding, sample-fastest, 4 per byte, low bits first (00 -> 2, 01 -> missing, 10 -> 1,
+ * 11 -> 0 copies of the counted allele), as rg_s2_qt_block_packed takes them; flip != 0 counts the other allele.
+ * Conventions: 0 on success, < 0 on error with rg_ld_last_error(ctx); the library never falls back to the CPU.
+ */
+#ifndef RG_LD_H
+#define RG_LD_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct rg_ld_ctx rg_ld_ctx;
+
+#define RG_LD_OK 0
+#define RG_LD_ERR_ARG (-1)
+#define RG_LD_ERR_HIP (-2)
+
+/* the three forms rg_ld_finish returns */
+#define RG_LD_R2_U16 0   /* uint16 [M (M - 1) / 2]: r * r * 65535 + 0.5 truncated, row-major over i < j (the binary .corr body) */
+#define RG_LD_CORR_F64 1 /* double [M][M]: the correlation matrix (the text .corr)                                             */
+#define RG_LD_COV_F64 2  /* double [M][M]: LD before the diagonal is looked at and before scaling                               */
+
+/* n analysed samples (1 <= n < 2^29), C covariate basis columns (intercept included; 1 <= C <= 64), M columns of the matrix
+ * (1 <= M <= 2^19; the M x M results and sums must fit the device: 8 M^2 bytes for LD, 4 M^2 per integer sum).  The packed rows
+ * of the M variants stay in device memory: M * 16 * ceil(n / 64) bytes. */
+int rg_ld_create(rg_ld_ctx** out, int device, int64_t n, int32_t n_cov, int32_t n_col);
+void rg_ld_destroy(rg_ld_ctx* ctx);
+const char* rg_ld_last_error(const rg_ld_ctx* ctx);
+
+/* X [C][n], orthonormal, sample-fastest (host pointer).  Needs n > C.  Before the first rg_ld_append that rg_ld_finish is to see. */
+int rg_ld_set_basis(rg_ld_ctx* ctx, const double* X);
+
+/* Columns that no variant fills (IDs forced into the matrix that the genotype file does not have): zero vectors, correlation 0
+ * with everything, diagonal 1.  cols: host, [k]. */
+int rg_ld_force_columns(rg_ld_ctx* ctx, int32_t k, const int32_t* cols);
+
+/* A panel of bs variants; row j (ld >= ceil(n / 4) bytes apart; host pointer, or device when rows_on_device) takes column cols[j]
+ * (host, [bs]) of the matrix.  A column can be given once. */
+int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, const int32_t* cols);
+
+/* The result in one of the three forms; out is a host pointer, or a device pointer when out_on_device (the quantisation runs on the
+ * device either way: M (M - 1) bytes leave it, not 8 M^2).  tol: a diagonal entry in (-tol, 0) zeroes its row and column
+ * (params.tol = 1e-8); numtol: a non-positive diagonal entry becomes numtol (params.numtol = 1e-6) -- Data.cpp:4386-4397.
+ * Every column must have been appended or forced. */
+int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol);
+
+/* Test entry: the raw integer sums of one panel pair, rows [a0, a0 + na) against rows [b0, b0 + nb) in the order they were
+ * appended (no basis needed): A[i][j] = sum g0_i g0_j, B[i][j] = sum g0_i miss_j, Bt[i][j] = sum miss_i g0_j, D[i][j] = sum miss_i miss_j,
+ * each int32 [na][nb] on the host; a NULL pointer skips that sum. */
+int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int32_t* A, int32_t* B, int32_t* Bt, int32_t* D);
+
+/* Device time of the panel-pair Gram kernel of the last rg_ld_finish / rg_ld_pair_sums, in ms, and the tiles it computed. */
+double rg_ld_last_kernel_ms(const rg_ld_ctx* ctx);
+int64_t rg_ld_last_tiles(const rg_ld_ctx* ctx);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

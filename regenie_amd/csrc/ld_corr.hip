@@ -1,0 +1,488 @@
+// The Step-2 LD matrix of a region (include/rg_ld.h): Data::print_ld (reference src/Data.cpp:4368-4449) on the matrix cores.
+//
+//   sum_s g_i g_j = A_ij + m_j B_ij + m_i B_ji + m_i m_j D_ij      A = g0 g0^T, B_ij = sum g0_i miss_j, D = miss miss^T   (exact int32)
+//   LD_ij         = sum_s g_i g_j - sum_c (X^T g_i)_c (X^T g_j)_c                                                          (fp64)
+//
+// k_ld_gram is the hot kernel: a 128 x 128 tile of row-panel variants against column-panel variants over all samples, both operands
+// read from the row store at 2 bits per genotype and expanded to int8 on the way to LDS (v_perm_b32 as a 4-entry byte LUT, as
+// gram_i8.hip does), contracted with v_mfma_i32_32x32x32_i8.  Against gram_i8.hip's tile it keeps the next K-step's 16 packed bytes
+// in flight in registers while the current one is multiplied, and double-buffers the LDS image so that a K-step costs one barrier.
+// Rows of the store are padded with code 11 (-> 0 for the dosage and for the indicator) to a multiple of 64 samples: the sample
+// tail is zero fill, there is no second kernel.  Only tile pairs on or above the diagonal are computed; the B / D passes leave at
+// once for tiles without a missing call.  X^T g_i comes from rg_s2_contract_packed (step2_qt.hip, exact digit planes).
+#include "rg_internal.h"
+#include "../../include/rg_ld.h"
+#include "../../include/rg_step2.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#define LT 128
+#define LPITCH 80  // 64 data bytes + 16 pad (gram_i8.hip: conflict-free ds_read_b128 fragment reads)
+#define LD_LUT_DOSAGE 0x00010002u  // 00 -> 2, 01 -> missing (0), 10 -> 1, 11 -> 0
+#define LD_LUT_MISS 0x00000100u
+
+namespace {
+
+__device__ __forceinline__ unsigned ld_expand4(unsigned b, unsigned lut) {
+  unsigned x = b | (b << 6);
+  x = x | (x << 12);
+  x &= 0x03030303u;
+  return __builtin_amdgcn_perm(lut, lut, x);
+}
+
+__device__ __forceinline__ void ld_stage(uint4 w, unsigned lut, uint8_t* lds_row) {
+  unsigned ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    uint4 o;
+    o.x = ld_expand4(ws[d] & 0xFFu, lut);
+    o.y = ld_expand4((ws[d] >> 8) & 0xFFu, lut);
+    o.z = ld_expand4((ws[d] >> 16) & 0xFFu, lut);
+    o.w = ld_expand4(ws[d] >> 24, lut);
+    *reinterpret_cast<uint4*>(lds_row + d * 16) = o;
+  }
+}
+
+// One 128 x 128 tile: C[r][c] = sum_k lutA(A[r][k]) * lutB(B[c][k]); rows of A and B are ld bytes apart, ld a multiple of 16.
+__device__ __forceinline__ void ld_tile(const uint8_t* __restrict__ A, int a_rows, unsigned a_lut, const uint8_t* __restrict__ B, int b_rows,
+                                        unsigned b_lut, bool same, int64_t ld, int32_t* __restrict__ C, int64_t ldc, uint8_t* smem) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  v16i acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
+
+  const bool isA = tid < LT;
+  const int srow = isA ? tid : tid - LT;
+  const bool do_stage = isA || !same;
+  const bool valid = do_stage && (isA ? srow < a_rows : srow < b_rows);
+  const uint8_t* gbase = isA ? A + (int64_t)srow * ld : B + (int64_t)srow * ld;
+  const unsigned lut = isA ? a_lut : b_lut;
+  const int my_off = (isA ? 0 : LT * LPITCH) + srow * LPITCH;
+  const int b_off = same ? 0 : LT * LPITCH;
+  const int64_t nk = ld / 16;
+  const uint4 pad = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);  // code 11 -> 0
+  uint4 w = pad;
+  if (valid) w = *reinterpret_cast<const uint4*>(gbase);
+  for (int64_t k = 0; k < nk; ++k) {
+    uint8_t* buf = smem + (k & 1) * (2 * LT * LPITCH);
+    if (do_stage) ld_stage(w, lut, buf + my_off);
+    if (valid && k + 1 < nk) w = *reinterpret_cast<const uint4*>(gbase + (k + 1) * 16);   // in flight while this step is multiplied
+    __syncthreads();   // the other buffer was read before the previous barrier: one barrier per step is enough
+    const uint8_t* sA = buf;
+    const uint8_t* sB = buf + b_off;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      v4i af[2], bf[2];
+      const int koff = ks * 32 + (lane >> 5) * 16;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const v4i*>(sA + (wr * 64 + i * 32 + (lane & 31)) * LPITCH + koff);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const v4i*>(sB + (wc * 64 + j * 32 + (lane & 31)) * LPITCH + koff);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i], bf[j], acc[i][j], 0, 0, 0);
+    }
+  }
+  // C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int col = wc * 64 + j * 32 + (lane & 31);
+        if (row < a_rows && col < b_rows) C[(int64_t)row * ldc + col] = acc[i][j][r];
+      }
+}
+
+// grid.x = tile pair, grid.y = which sum (0: A, 1: B, 2: B of the mirrored pair / Bt, 3: D).
+//   tri != 0 (rg_ld_finish): rows [0, na) against themselves, tile pairs tr <= tc only; SA, SD [na][na] (upper tiles written),
+//     SB [na][na] full: y = 1 writes tile (tr, tc) of it, y = 2 tile (tc, tr); tile_miss[t] != 0: tile t has a missing call.
+//   kinds: bit k set = sum k is wanted.
+//   tri == 0 (rg_ld_pair_sums): rows [a0, a0 + na) against [b0, b0 + nb), every tile pair and every sum; SBt [na][nb] is y = 2.
+__global__ __launch_bounds__(256) void k_ld_gram(const uint8_t* __restrict__ rows, int64_t ld, int a0, int na, int b0, int nb, int tri, int kinds,
+                                                 const uint8_t* __restrict__ tile_miss, int32_t* SA, int32_t* SB, int32_t* SBt, int32_t* SD, int64_t ldc) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * 2 * LT * LPITCH];
+  const int nta = (na + LT - 1) / LT, ntb = (nb + LT - 1) / LT;
+  int tidx = blockIdx.x;
+  {  // XCD-aware remap (gram_i8.hip): consecutive tile ids share an operand panel; keep them on one XCD's L2
+    const int nwg = gridDim.x;
+    const int q = nwg / 8, r = nwg % 8, xcd = tidx % 8, k = tidx / 8;
+    tidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  }
+  int tr, tc;
+  if (tri) {  // unrank over tc >= tr: pair index = tc (tc + 1) / 2 + tr
+    tc = (int)((sqrtf(8.0f * tidx + 1.0f) - 1.0f) * 0.5f);
+    while ((tc + 1) * (tc + 2) / 2 <= tidx) ++tc;
+    while (tc * (tc + 1) / 2 > tidx) --tc;
+    tr = tidx - tc * (tc + 1) / 2;
+  } else {
+    tr = tidx / ntb;
+    tc = tidx - tr * ntb;
+  }
+  if (tr >= nta || tc >= ntb) return;
+  const int kind = blockIdx.y;
+  if (!((kinds >> kind) & 1)) return;      // a sum the caller did not ask for
+  const uint8_t* Ar = rows + (int64_t)(a0 + tr * LT) * ld;
+  const uint8_t* Bc = rows + (int64_t)(b0 + tc * LT) * ld;
+  const int ar = min(LT, na - tr * LT), bc = min(LT, nb - tc * LT);
+  const bool diag = tri && tr == tc;
+  if (kind == 0) {
+    ld_tile(Ar, ar, LD_LUT_DOSAGE, Bc, bc, LD_LUT_DOSAGE, diag, ld, SA + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  } else if (kind == 1) {
+    if (tile_miss && !tile_miss[tc]) return;
+    ld_tile(Ar, ar, LD_LUT_DOSAGE, Bc, bc, LD_LUT_MISS, false, ld, SB + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  } else if (kind == 2) {
+    if (tri) {  // B of the mirrored pair: dosage of tile tc against the indicator of tile tr
+      if (diag || (tile_miss && !tile_miss[tr])) return;
+      ld_tile(Bc, bc, LD_LUT_DOSAGE, Ar, ar, LD_LUT_MISS, false, ld, SB + (int64_t)tc * LT * ldc + (int64_t)tr * LT, ldc, smem);
+    } else {
+      ld_tile(Ar, ar, LD_LUT_MISS, Bc, bc, LD_LUT_DOSAGE, false, ld, SBt + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+    }
+  } else {
+    if (tile_miss && !(tile_miss[tr] && tile_miss[tc])) return;
+    ld_tile(Ar, ar, LD_LUT_MISS, Bc, bc, LD_LUT_MISS, diag, ld, SD + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  }
+}
+
+// Rows as they arrive (nbytes = ceil(n / 4) bytes used, ld bytes apart, already copied into the store) -> the store's form:
+// the other allele when flip, the codes past sample n and the padding up to ld set to 11.  One workgroup per row.
+__global__ __launch_bounds__(256) void k_ld_store(uint8_t* __restrict__ rows, int64_t ld, int64_t n, int flip) {
+  uint8_t* row = rows + (int64_t)blockIdx.x * ld;
+  const int64_t nbytes = (n + 3) / 4;
+  for (int64_t b = threadIdx.x; b < ld; b += blockDim.x) {
+    unsigned v = b < nbytes ? row[b] : 0xFFu;
+    if (flip) {  // 00 <-> 11, 01 and 10 stay
+      const unsigned eq = ~((v >> 1) ^ v) & 0x55u;
+      v ^= eq | (eq << 1);
+    }
+    if (b == nbytes - 1 && (n & 3)) v |= (0xFFu << (2 * (n & 3))) & 0xFFu;
+    if (b >= nbytes) v = 0xFFu;
+    row[b] = (uint8_t)v;
+  }
+}
+
+// LD[ci][cj] for the row pair (i, j), i <= j, written to both triangles of the M x M matrix.
+__global__ __launch_bounds__(256) void k_ld_combine(const int32_t* __restrict__ SA, const int32_t* __restrict__ SB, const int32_t* __restrict__ SD,
+                                                    int R, const double* __restrict__ mean, const double* __restrict__ gx, int C,
+                                                    const int32_t* __restrict__ col, double* __restrict__ LD, int M) {
+  const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= R || j >= R || i > j) return;
+  double v = (double)SA[(int64_t)i * R + j];
+  if (SB) {
+    const double mi = mean[i], mj = mean[j];
+    v = __dadd_rn(v, __dmul_rn(mj, (double)SB[(int64_t)i * R + j]));
+    v = __dadd_rn(v, __dmul_rn(mi, (double)SB[(int64_t)j * R + i]));
+    v = __dadd_rn(v, __dmul_rn(__dmul_rn(mi, mj), (double)SD[(int64_t)i * R + j]));
+  }
+  double p = 0.0;
+  for (int c = 0; c < C; ++c) p = fma(gx[(int64_t)i * C + c], gx[(int64_t)j * C + c], p);
+  v -= p;
+  const int ci = col[i], cj = col[j];
+  LD[(int64_t)ci * M + cj] = v;
+  LD[(int64_t)cj * M + ci] = v;
+}
+
+// Data.cpp:4386-4397: zero[c] = diagonal in (-tol, 0); sds[c] = sqrt(numtol) for a non-positive diagonal (a zeroed one included)
+__global__ void k_ld_diag(const double* __restrict__ LD, int M, double tol, double numtol, uint8_t* __restrict__ zero, double* __restrict__ inv_sd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= M) return;
+  const double d = LD[(int64_t)c * M + c];
+  const bool z = d < 0 && fabs(d) < tol;
+  zero[c] = z ? 1 : 0;
+  const double sd = (z || d <= 0) ? sqrt(numtol) : sqrt(d);
+  inv_sd[c] = 1.0 / sd;
+}
+
+__device__ __forceinline__ double ld_corr_at(const double* __restrict__ LD, int M, const uint8_t* __restrict__ zero, const double* __restrict__ inv_sd,
+                                             int i, int j) {
+  if (i == j) {  // the diagonal becomes sds^2 before the scaling
+    const double sd = 1.0 / inv_sd[i];
+    return __dmul_rn(__dmul_rn(inv_sd[i], __dmul_rn(sd, sd)), inv_sd[i]);
+  }
+  const double v = (zero[i] || zero[j]) ? 0.0 : LD[(int64_t)i * M + j];
+  return __dmul_rn(__dmul_rn(inv_sd[i], v), inv_sd[j]);
+}
+
+__global__ __launch_bounds__(256) void k_ld_corr(const double* __restrict__ LD, int M, const uint8_t* __restrict__ zero, const double* __restrict__ inv_sd,
+                                                 double* __restrict__ out) {
+  const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= M || j >= M) return;
+  out[(int64_t)i * M + j] = ld_corr_at(LD, M, zero, inv_sd, min(i, j), max(i, j));
+}
+
+// print_ld's binary body: vals(k++) = r * r * 65535 + 0.5 over i < j, truncated to 16 bits (no fused multiply-add: the value is
+// the one the host would compute from the correlation)
+__global__ __launch_bounds__(256) void k_ld_r2(const double* __restrict__ LD, int M, const uint8_t* __restrict__ zero, const double* __restrict__ inv_sd,
+                                               uint16_t* __restrict__ out) {
+  const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= M || j >= M || i >= j) return;
+  const double r = ld_corr_at(LD, M, zero, inv_sd, i, j);
+  const double v = __dadd_rn(__dmul_rn(__dmul_rn(r, r), 65535.0), 0.5);
+  const int64_t k = (int64_t)i * M - (int64_t)i * (i + 1) / 2 + (j - i - 1);
+  out[k] = (uint16_t)(v < 65535.0 ? (unsigned)v : 65535u);
+}
+
+}  // namespace
+
+struct rg_ld_ctx {
+  int dev = 0;
+  int64_t n = 0, ld = 0;
+  int C = 0, M = 0, nrows = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  uint8_t* rows = nullptr;            // [M][ld] in the order appended
+  rg_s2_ctx* s2 = nullptr;            // the contraction primitive (X^T g), created by rg_ld_set_basis
+  std::vector<int32_t> col_of_row;    // [nrows]
+  std::vector<uint8_t> col_state;     // [M] 0: open, 1: appended, 2: forced
+  std::vector<double> mean, gx;       // [nrows], [nrows][C]
+  std::vector<int32_t> nmiss;         // [nrows]
+  double last_ms = 0.0;
+  int64_t last_tiles = 0;
+  std::string err;
+};
+
+static int ld_fail(rg_ld_ctx* ctx, int code, const std::string& msg) {
+  if (ctx) ctx->err = msg;
+  return code;
+}
+#define LD_HIP(x)                                                                                                              \
+  do {                                                                                                                         \
+    hipError_t e_ = (x);                                                                                                       \
+    if (e_ != hipSuccess) return ld_fail(ctx, RG_LD_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));                   \
+  } while (0)
+
+namespace {
+struct DevBuf {  // device memory of one call
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  template <class T> T* as() const { return (T*)p; }
+};
+}  // namespace
+
+extern "C" {
+
+int rg_ld_create(rg_ld_ctx** out, int device, int64_t n, int32_t n_cov, int32_t n_col) {
+  if (!out) return RG_LD_ERR_ARG;
+  rg_ld_ctx* ctx = new rg_ld_ctx();
+  *out = ctx;
+  if (n < 1 || n >= ((int64_t)1 << 29)) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_create: need 1 <= n < 2^29 samples (int32 sums)");
+  if (n_col < 1 || n_col > (1 << 19)) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_create: need 1 <= M <= 2^19 columns");
+  if (n_cov < 1 || n_cov > RG_S2_MAX_COV) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_create: need 1 <= n_cov <= 64");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ld_fail(ctx, RG_LD_ERR_HIP, "rg_ld_create: no HIP device (this library has no CPU path)");
+  if (device < 0 || device >= ndev) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_create: device index out of range");
+  ctx->dev = device; ctx->n = n; ctx->C = n_cov; ctx->M = n_col;
+  ctx->ld = (n + 63) / 64 * 16;
+  LD_HIP(hipSetDevice(device));
+  LD_HIP(hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking));
+  LD_HIP(hipEventCreate(&ctx->e0));
+  LD_HIP(hipEventCreate(&ctx->e1));
+  LD_HIP(hipMalloc((void**)&ctx->rows, (size_t)n_col * ctx->ld));
+  ctx->col_state.assign(n_col, 0);
+  return RG_LD_OK;
+}
+
+void rg_ld_destroy(rg_ld_ctx* ctx) {
+  if (!ctx) return;
+  if (ctx->st) {
+    (void)hipSetDevice(ctx->dev);
+    (void)hipStreamSynchronize(ctx->st);
+    if (ctx->s2) rg_s2_destroy(ctx->s2);
+    if (ctx->rows) (void)hipFree(ctx->rows);
+    if (ctx->e0) (void)hipEventDestroy(ctx->e0);
+    if (ctx->e1) (void)hipEventDestroy(ctx->e1);
+    (void)hipStreamDestroy(ctx->st);
+  }
+  delete ctx;
+}
+
+const char* rg_ld_last_error(const rg_ld_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+double rg_ld_last_kernel_ms(const rg_ld_ctx* ctx) { return ctx ? ctx->last_ms : 0.0; }
+int64_t rg_ld_last_tiles(const rg_ld_ctx* ctx) { return ctx ? ctx->last_tiles : 0; }
+
+int rg_ld_set_basis(rg_ld_ctx* ctx, const double* X) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_set_basis: context was not created");
+  if (!X) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_set_basis: null argument");
+  if (ctx->nrows > 0) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_set_basis: the basis must be set before the first panel is appended");
+  if (ctx->n <= ctx->C) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_set_basis: need n > n_cov");
+  if (!ctx->s2) {
+    if (rg_s2_create(&ctx->s2, ctx->dev, ctx->n, ctx->C, 1) != RG_S2_OK) {
+      const std::string m = std::string("rg_ld_set_basis: ") + rg_s2_last_error(ctx->s2);
+      rg_s2_destroy(ctx->s2);
+      ctx->s2 = nullptr;
+      return ld_fail(ctx, RG_LD_ERR_HIP, m);
+    }
+  }
+  if (rg_s2_set_columns(ctx->s2, ctx->C, X, 0) != RG_S2_OK) return ld_fail(ctx, RG_LD_ERR_HIP, std::string("rg_ld_set_basis: ") + rg_s2_last_error(ctx->s2));
+  return RG_LD_OK;
+}
+
+int rg_ld_force_columns(rg_ld_ctx* ctx, int32_t k, const int32_t* cols) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_force_columns: context was not created");
+  if (k < 0 || (k > 0 && !cols)) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_force_columns: bad arguments");
+  for (int t = 0; t < k; ++t) {
+    if (cols[t] < 0 || cols[t] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_force_columns: column index out of range");
+    if (ctx->col_state[cols[t]] == 1) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_force_columns: column " + std::to_string(cols[t]) + " holds a variant already");
+  }
+  for (int t = 0; t < k; ++t) ctx->col_state[cols[t]] = 2;
+  return RG_LD_OK;
+}
+
+int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, const int32_t* cols) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: context was not created");
+  const int64_t n = ctx->n, nbytes = (n + 3) / 4;
+  if (!rows || !cols || bs < 1 || ld < nbytes) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: bad arguments (need bs >= 1, ld >= ceil(n / 4))");
+  if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
+  {
+    std::vector<uint8_t> seen(ctx->col_state);
+    for (int j = 0; j < bs; ++j) {
+      if (cols[j] < 0 || cols[j] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: column index out of range");
+      if (seen[cols[j]]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: column " + std::to_string(cols[j]) + " is used twice");
+      seen[cols[j]] = 1;
+    }
+  }
+  LD_HIP(hipSetDevice(ctx->dev));
+  uint8_t* dst = ctx->rows + (int64_t)ctx->nrows * ctx->ld;
+  LD_HIP(hipMemcpy2DAsync(dst, ctx->ld, rows, ld, nbytes, bs, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
+  hipLaunchKernelGGL(k_ld_store, dim3(bs), dim3(256), 0, ctx->st, dst, ctx->ld, n, flip ? 1 : 0);
+  LD_HIP(hipGetLastError());
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  const int r0 = ctx->nrows, C = ctx->C;
+  ctx->mean.resize((size_t)r0 + bs, 0.0);
+  ctx->nmiss.resize((size_t)r0 + bs, 0);
+  ctx->gx.resize(((size_t)r0 + bs) * C, 0.0);
+  if (ctx->s2) {  // X^T g0, X^T miss and the call counts of the stored rows (the allele is already the one counted)
+    std::vector<double> sums((size_t)bs * 2 * C);
+    std::vector<int32_t> counts((size_t)bs * 4);
+    rg_s2_contract_out co = {sums.data(), nullptr, counts.data(), nullptr};
+    if (rg_s2_contract_packed(ctx->s2, dst, ctx->ld, bs, 1, 0, &co) != RG_S2_OK)
+      return ld_fail(ctx, RG_LD_ERR_HIP, std::string("rg_ld_append: ") + rg_s2_last_error(ctx->s2));
+    for (int j = 0; j < bs; ++j) {
+      const int32_t* c4 = counts.data() + (size_t)j * 4;
+      const int64_t nobs = n - c4[2];
+      const double m = nobs > 0 ? (double)((int64_t)c4[0] + 2 * (int64_t)c4[1]) / (double)nobs : 0.0;
+      ctx->mean[r0 + j] = m;
+      ctx->nmiss[r0 + j] = c4[2];
+      for (int c = 0; c < C; ++c) ctx->gx[(size_t)(r0 + j) * C + c] = sums[((size_t)j * 2) * C + c] + m * sums[((size_t)j * 2 + 1) * C + c];
+    }
+  }
+  for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
+  ctx->nrows += bs;
+  return RG_LD_OK;
+}
+
+int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int32_t* A, int32_t* B, int32_t* Bt, int32_t* D) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: context was not created");
+  if (a0 < 0 || b0 < 0 || na < 1 || nb < 1 || (int64_t)a0 + na > ctx->nrows || (int64_t)b0 + nb > ctx->nrows)
+    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: row range outside the panels appended");
+  LD_HIP(hipSetDevice(ctx->dev));
+  const size_t cnt = (size_t)na * nb;
+  DevBuf S;
+  LD_HIP(S.alloc(4 * cnt * sizeof(int32_t)));
+  int32_t* s = S.as<int32_t>();
+  const int nt = ((na + LT - 1) / LT) * ((nb + LT - 1) / LT);
+  const int kinds = (A ? 1 : 0) | (B ? 2 : 0) | (Bt ? 4 : 0) | (D ? 8 : 0);
+  LD_HIP(hipEventRecord(ctx->e0, ctx->st));
+  hipLaunchKernelGGL(k_ld_gram, dim3(nt, 4), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s, s + cnt, s + 2 * cnt,
+                     s + 3 * cnt, (int64_t)nb);
+  LD_HIP(hipGetLastError());
+  LD_HIP(hipEventRecord(ctx->e1, ctx->st));
+  int32_t* outs[4] = {A, B, Bt, D};
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) LD_HIP(hipMemcpyAsync(outs[k], s + k * cnt, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  float ms = 0.f;
+  LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+  ctx->last_ms = ms;
+  ctx->last_tiles = (int64_t)nt * __builtin_popcount(kinds);
+  return RG_LD_OK;
+}
+
+int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: context was not created");
+  if (!out || (form != RG_LD_R2_U16 && form != RG_LD_CORR_F64 && form != RG_LD_COV_F64) || !(numtol > 0) || !(tol >= 0))
+    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: bad arguments");
+  if (!ctx->s2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: rg_ld_set_basis has not been called");
+  const int M = ctx->M, R = ctx->nrows, C = ctx->C;
+  for (int c = 0; c < M; ++c)
+    if (!ctx->col_state[c]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: column " + std::to_string(c) + " was neither appended nor forced");
+  LD_HIP(hipSetDevice(ctx->dev));
+  const int nt = (R + LT - 1) / LT;
+  std::vector<uint8_t> tile_miss(std::max(1, nt), 0);
+  bool any_miss = false;
+  for (int r = 0; r < R; ++r) if (ctx->nmiss[r] > 0) { tile_miss[r / LT] = 1; any_miss = true; }
+  DevBuf dLD, dSA, dSB, dSD, dTm, dMean, dGx, dCol, dZero, dInv, dOut;
+  const size_t MM = (size_t)M * M, RR = (size_t)R * R;
+  LD_HIP(dLD.alloc(MM * sizeof(double)));
+  LD_HIP(hipMemsetAsync(dLD.p, 0, MM * sizeof(double), ctx->st));
+  ctx->last_ms = 0.0;
+  ctx->last_tiles = 0;
+  if (R > 0) {
+    LD_HIP(dSA.alloc(RR * sizeof(int32_t)));
+    if (any_miss) {
+      LD_HIP(dSB.alloc(RR * sizeof(int32_t)));
+      LD_HIP(dSD.alloc(RR * sizeof(int32_t)));
+      LD_HIP(hipMemsetAsync(dSB.p, 0, RR * sizeof(int32_t), ctx->st));
+      LD_HIP(hipMemsetAsync(dSD.p, 0, RR * sizeof(int32_t), ctx->st));
+    }
+    LD_HIP(dTm.alloc(tile_miss.size()));
+    LD_HIP(dMean.alloc(sizeof(double) * R));
+    LD_HIP(dGx.alloc(sizeof(double) * R * C));
+    LD_HIP(dCol.alloc(sizeof(int32_t) * R));
+    LD_HIP(hipMemcpyAsync(dTm.p, tile_miss.data(), tile_miss.size(), hipMemcpyHostToDevice, ctx->st));
+    LD_HIP(hipMemcpyAsync(dMean.p, ctx->mean.data(), sizeof(double) * R, hipMemcpyHostToDevice, ctx->st));
+    LD_HIP(hipMemcpyAsync(dGx.p, ctx->gx.data(), sizeof(double) * R * C, hipMemcpyHostToDevice, ctx->st));
+    LD_HIP(hipMemcpyAsync(dCol.p, ctx->col_of_row.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->st));
+    const int npair = nt * (nt + 1) / 2;
+    LD_HIP(hipEventRecord(ctx->e0, ctx->st));
+    hipLaunchKernelGGL(k_ld_gram, dim3(npair, any_miss ? 4 : 1), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, 0, R, 0, R, 1, 0xF, dTm.as<uint8_t>(), dSA.as<int32_t>(),
+                       dSB.as<int32_t>(), (int32_t*)nullptr, dSD.as<int32_t>(), (int64_t)R);
+    LD_HIP(hipGetLastError());
+    LD_HIP(hipEventRecord(ctx->e1, ctx->st));
+    int64_t tiles = npair;
+    if (any_miss)
+      for (int a = 0; a < nt; ++a)
+        for (int b = a; b < nt; ++b) tiles += (tile_miss[b] ? 1 : 0) + ((a != b && tile_miss[a]) ? 1 : 0) + ((tile_miss[a] && tile_miss[b]) ? 1 : 0);
+    ctx->last_tiles = tiles;
+    const dim3 g2((R + 15) / 16, (R + 15) / 16);
+    hipLaunchKernelGGL(k_ld_combine, g2, dim3(256), 0, ctx->st, dSA.as<int32_t>(), any_miss ? dSB.as<int32_t>() : (const int32_t*)nullptr, dSD.as<int32_t>(), R,
+                       dMean.as<double>(), dGx.as<double>(), C, dCol.as<int32_t>(), dLD.as<double>(), M);
+    LD_HIP(hipGetLastError());
+  }
+  const dim3 gM((M + 15) / 16, (M + 15) / 16);
+  const size_t out_bytes = form == RG_LD_R2_U16 ? (size_t)M * (M - 1) / 2 * sizeof(uint16_t) : MM * sizeof(double);
+  void* dres = nullptr;
+  if (form == RG_LD_COV_F64) dres = dLD.p;
+  else {
+    LD_HIP(dZero.alloc(M));
+    LD_HIP(dInv.alloc(sizeof(double) * M));
+    hipLaunchKernelGGL(k_ld_diag, dim3((M + 255) / 256), dim3(256), 0, ctx->st, dLD.as<double>(), M, tol, numtol, dZero.as<uint8_t>(), dInv.as<double>());
+    LD_HIP(hipGetLastError());
+    if (out_on_device) dres = out;
+    else { LD_HIP(dOut.alloc(out_bytes)); dres = dOut.p; }
+    if (form == RG_LD_CORR_F64) hipLaunchKernelGGL(k_ld_corr, gM, dim3(256), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(), dInv.as<double>(), (double*)dres);
+    else if (M > 1) hipLaunchKernelGGL(k_ld_r2, gM, dim3(256), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(), dInv.as<double>(), (uint16_t*)dres);
+    LD_HIP(hipGetLastError());
+  }
+  if (dres != out && out_bytes > 0) LD_HIP(hipMemcpyAsync(out, dres, out_bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  if (R > 0) {
+    float ms = 0.f;
+    LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+    ctx->last_ms = ms;
+  }
+  return RG_LD_OK;
+}
+
+}  // extern "C"

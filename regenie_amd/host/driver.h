@@ -19,6 +19,7 @@
 //   driver_models.cpp  covariate-only null models and the host-side statistics (logistic / Poisson / Cox null fits, Firth, p-values)
 //   driver_inputs.cpp  genotype metadata (.bim/.fam, .pvar/.psam, .bgen), phenotype / covariate files, LOCO files, the level-0 job files
 //   driver_step2.cpp   `--step 2`: single-variant tests on the rg_step2.h kernels, one part per GPU
+//   driver_ld.cpp      `--step 2 --compute-corr`: the LD matrix of a region on the rg_ld.h kernels
 //   driver_step1.cpp   `--step 1`: streamed ingest, level 0, the multi-GPU exchange, level 1, the .loco / .prs writers; run()
 //   driver_main.cpp    main()
 #pragma once
@@ -59,6 +60,7 @@
 #include "../../include/rg_pgen.h"
 #include "../../include/rg_step1.h"
 #include "../../include/rg_step2.h"
+#include "../../include/rg_ld.h"
 
 namespace rgdrv {
 
@@ -105,6 +107,13 @@ struct Params {
   // --step 2 (single-variant association test, quantitative traits: Data::test_snps_fast, Data.cpp:2230-2360)
   std::string pred_list;    // --pred: the _pred.list of step 1
   double min_mac = 5;       // --minMAC (Regenie.hpp:311)
+  // --chr / --chrList / --range: the variant filter of read_bim / read_pvar / the .bgen index (Geno.cpp:106-110, :582-587, :857-859)
+  std::set<int> chr_keep;   // empty: every chromosome
+  bool set_range = false;
+  int range_chr = -1;
+  double range_min = 0, range_max = 0;
+  // --step 2 --compute-corr: the LD matrix of a region (Data::ld_comp, Data.cpp:3807-3848; driver_ld.cpp)
+  bool compute_corr = false, corr_text = false, forcein_vars = false;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards
@@ -327,6 +336,9 @@ void prep_parallel_l0(Run& r);
 void prep_parallel_l1(Run& r, int total_n_block, int64_t n_variants);
 // ---- driver_step2.cpp / driver_step1.cpp
 int run_step2_all(Run& r, std::chrono::steady_clock::time_point t_start);
+// driver_ld.cpp registers its entry here when it is linked in: a build of the driver without that unit (the host-emulated test binary) still
+// links, and says so when asked for the mode
+extern int (*run_ld_entry)(Run& r, std::chrono::steady_clock::time_point t_start);
 int run(int argc, char** argv);
 
 }  // namespace rgdrv

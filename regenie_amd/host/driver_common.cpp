@@ -257,6 +257,8 @@ void jacobi_eigh(std::vector<double> A, int n, std::vector<double>& d, std::vect
   V.swap(V2);
 }
 
+int (*run_ld_entry)(Run&, std::chrono::steady_clock::time_point) = nullptr;
+
 [[noreturn]] void usage_error(const std::string& m) { throw std::runtime_error(m); }
 
 Params parse_args(int argc, char** argv) {
@@ -269,6 +271,8 @@ Params parse_args(int argc, char** argv) {
     for (auto& s : split_char(v, ',')) dst.push_back(s);
   };
   bool saw_pheno_col = false, saw_pheno_collist = false;
+  std::vector<std::string> saw_chr;
+  std::string range_chr_str;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--step") p.step = atoi(need(i).c_str());
@@ -349,6 +353,21 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--use-null-firth") p.use_null_firth = need(i);
     else if (a == "--pThresh") p.pthresh = atof(need(i).c_str());
     else if (a == "--spa") p.spa = true;
+    else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
+    else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
+    else if (a == "--forcein-vars") p.forcein_vars = true;
+    else if (a == "--ld-extract") { need(i); usage_error("--ld-extract (burden masks in the LD matrix) is not built: use --extract [--forcein-vars] for single variants."); }
+    else if (a == "--skip-scaleG") usage_error("--skip-scaleG (the LD matrix of unscaled genotypes) is not built.");
+    else if (a == "--sparse-thr") { need(i); usage_error("--sparse-thr (the sparsified LD matrix, which needs --skip-scaleG) is not built."); }
+    else if (a == "--chr") { const std::string v = need(i); saw_chr.push_back(v); }           // Regenie.cpp:650-655
+    else if (a == "--chrList") { for (auto& s : split_char(need(i), ',')) saw_chr.push_back(s); }   // Regenie.cpp:643-649
+    else if (a == "--range") {                                                                // Regenie.cpp:741-755
+      const std::string v = need(i);
+      char chr[21];
+      double p0 = -1, p1 = -1;
+      if (sscanf(v.c_str(), "%20[^:]:%lf-%lf", chr, &p0, &p1) != 3 || p0 < 0 || p1 < 0) usage_error("wrong format for --range (must be CHR:MINPOS-MAXPOS).");
+      p.set_range = true; range_chr_str = chr; p.range_min = std::min(p0, p1); p.range_max = std::max(p0, p1);
+    }
     else usage_error("unrecognised option '" + a + "'");
   }
   if (p.bt) p.rint = false;  // Regenie.cpp:432
@@ -368,7 +387,24 @@ Params parse_args(int argc, char** argv) {
     p.run_l0 = p.run_l1 = p.split_l0 = false;
   }
   if (p.n_block > 0 && p.step == 2) usage_error("--nb in step 2 is not built (it limits the blocks of a step 1 run here).");
-  if (p.step == 2) {
+  for (auto& s : saw_chr) {      // --nauto may come after --chr: the names are resolved once every option is read
+    const int c = chr_str_to_int(s, p.nchrom);
+    if (c <= 0) usage_error("invalid chromosome specified by --chr/--chrList.");      // Regenie.cpp:1167
+    p.chr_keep.insert(c);
+  }
+  if (p.set_range) {
+    p.range_chr = chr_str_to_int(range_chr_str, p.nchrom);
+    if (p.range_chr <= 0) usage_error("unrecognized chromosome in --range.");          // Regenie.cpp:1153-1154
+  }
+  if (p.compute_corr) {          // Regenie.cpp:522-535
+    if (p.step != 2) usage_error("--compute-corr / --output-corr-text need --step 2.");
+    if (!p.exclude.empty()) usage_error("cannot use --exclude with --compute-corr (use --extract instead)");
+    if (!p.bgen.empty()) usage_error("--compute-corr with dosage input (--bgen) is not built: the LD matrix is computed from hard calls (--bed, or a .pgen without a dosage track).");
+    if (p.gpus > 1) usage_error("--compute-corr on more than one GPU (--gpus) is not built.");
+    if (p.forcein_vars && p.extract.size() > 1) usage_error("cannot have multiple extract files");      // Geno.cpp:1352
+    p.forcein_vars = p.forcein_vars && !p.extract.empty();
+  }
+  if (p.step == 2 && !p.compute_corr) {
     if (p.pred_list.empty()) usage_error("option '--pred' is required (use the _pred.list file written by step 1).");
     if (p.firth && !p.bt) usage_error("option '--firth' applies to binary traits (--bt).");
     if (p.spa && !p.bt) usage_error("option '--spa' applies to binary traits (--bt).");
@@ -385,7 +421,7 @@ Params parse_args(int argc, char** argv) {
     p.write_null_firth = false;
   }
   if ((int)!p.bed.empty() + (int)!p.pgen.empty() + (int)!p.bgen.empty() != 1) usage_error("must use either --bed,--bgen or --pgen.");  // Regenie.cpp:419-420
-  if (p.pheno_file.empty()) usage_error("option '--phenoFile' is required.");
+  if (p.pheno_file.empty() && !p.compute_corr) usage_error("option '--phenoFile' is required.");      // Regenie.cpp:1303
   if (p.bsize < 1) usage_error("must specify the block size using '--bsize'.");
   if (p.cv_folds < 2) usage_error("number of CV folds must be at least 2");
   if (p.gpus < 1) usage_error("--gpus must be at least 1");

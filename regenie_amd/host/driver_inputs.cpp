@@ -40,7 +40,7 @@ void read_bgen_meta(Run& r) {
     if (!exclude_files.empty() && exc.count(rsid)) keep = false;
     if (keep) {
       r.snp_chrom.push_back(c); r.snp_offset.push_back(j); r.snp_ids.push_back(rsid);
-      if (p.step == 2) {   // prep_bgen (Geno.cpp:80-86): allele0 is the file's second allele unless --ref-first ("switch so allele0 is ALT")
+      if (p.step == 2 || p.set_range) {   // prep_bgen (Geno.cpp:80-86): allele0 is the file's second allele unless --ref-first ("switch so allele0 is ALT")
         r.snp_pos.push_back((int64_t)position);
         r.snp_a0.push_back(p.ref_first ? al0 : al1);
         r.snp_a1.push_back(p.ref_first ? al1 : al0);
@@ -218,11 +218,11 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
       if (!exclude_files.empty() && exc.count(vid)) keep = false;
       if (keep) {
         r.snp_chrom.push_back(c); r.snp_offset.push_back(lineno); r.snp_ids.push_back(vid);
-        if (!pg && p.step == 2) {   // read_bim (Geno.cpp:546-553): the reference allele is the LAST one unless --ref-first
+        if (!pg && (p.step == 2 || p.set_range)) {   // read_bim (Geno.cpp:546-553): the reference allele is the LAST one unless --ref-first
           r.snp_pos.push_back((int64_t)std::strtoul(t[3].c_str(), nullptr, 0));
           r.snp_a0.push_back(p.ref_first ? t[4] : t[5]);
           r.snp_a1.push_back(p.ref_first ? t[5] : t[4]);
-        } else if (pg && p.step == 2) {   // read_pvar (Geno.cpp:824-828): allele1 = REF, allele2 = ALT, whatever --ref-first says
+        } else if (pg && (p.step == 2 || p.set_range)) {   // read_pvar (Geno.cpp:824-828): allele1 = REF, allele2 = ALT, whatever --ref-first says
           if (std::max(pos_col, std::max(ref_col, alt_col)) >= t.size())
             throw std::runtime_error("incorrectly formatted " + kind + " file at line " + std::to_string(lineno + 1));
           r.snp_pos.push_back((int64_t)std::strtoul(t[pos_col].c_str(), nullptr, 0));
@@ -283,6 +283,28 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
 
 void apply_sample_and_variant_filters(Run& r) {
   const Params& p = r.p;
+  // --chr / --chrList / --range (in_chrList, in_range: Geno.cpp:2714-2800; applied while the variant file is read, :582-587)
+  if (!p.chr_keep.empty() || p.set_range) {
+    if (p.set_range && r.snp_pos.size() != r.snp_chrom.size()) throw std::runtime_error("--range is not built for this genotype input in step 1 (no positions are kept).");
+    size_t w = 0;
+    for (size_t j = 0; j < r.snp_chrom.size(); ++j) {
+      const int c = r.snp_chrom[j];
+      if (!p.chr_keep.empty() && !p.chr_keep.count(c)) continue;
+      if (p.set_range && (c != p.range_chr || (double)r.snp_pos[j] < p.range_min || (double)r.snp_pos[j] > p.range_max)) continue;
+      if (w != j) {
+        r.snp_chrom[w] = c; r.snp_offset[w] = r.snp_offset[j]; r.snp_ids[w] = std::move(r.snp_ids[j]);
+        if (!r.snp_pos.empty()) { r.snp_pos[w] = r.snp_pos[j]; r.snp_a0[w] = std::move(r.snp_a0[j]); r.snp_a1[w] = std::move(r.snp_a1[j]); }
+      }
+      ++w;
+    }
+    r.snp_chrom.resize(w); r.snp_offset.resize(w); r.snp_ids.resize(w);
+    if (!r.snp_pos.empty()) { r.snp_pos.resize(w); r.snp_a0.resize(w); r.snp_a1.resize(w); }
+    std::vector<int> chr_left;      // a chromosome without a variant left has no block
+    for (int c : r.chr_read) if (std::find(r.snp_chrom.begin(), r.snp_chrom.end(), c) != r.snp_chrom.end()) chr_left.push_back(c);
+    r.chr_read.swap(chr_left);
+    if (p.set_range) sout << "   -number of variants after filtering on range = " << w << "\n";      // Geno.cpp:1139-1140
+    if (w == 0) throw std::runtime_error("no variant left to include in analysis.");
+  }
   // --keep / --remove (Geno.cpp:1263-1341)
   r.ind_ignore.assign(r.n_file, 0);
   if (!p.remove.empty()) {
@@ -401,7 +423,13 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
   const IdIndex ids(r.ids);                          // the sample files: FID / IID token pairs -> sample, no key string built
   const int nt_parse = std::max(1, std::min(32, usable_cpus() - 1));
   std::vector<uint8_t> in_pheno(N, 0), in_cov(N, p.covar_file.empty() ? 1 : 0);
-  {
+  if (p.compute_corr) {      // Pheno.cpp:55-61: no phenotype file is read; one constant "phenotype", nobody masked
+    r.P = 1;
+    r.pheno_names.assign(1, "Y1");
+    r.Y.assign((size_t)N, 1.0);
+    r.mask.assign((size_t)N, 1);
+    in_pheno.assign(N, 1);
+  } else {
     TextIn f(p.pheno_file);
     if (!f) throw std::runtime_error("cannot open file : " + p.pheno_file);
     sout << std::left << std::setw(20) << " * phenotypes" << ": [" << p.pheno_file << "] ";
@@ -557,7 +585,7 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
     for (int64_t i = 0; i < N; ++i) np += in_pheno[i];
     sout << "   -number of phenotyped individuals " << (strict ? "with no missing data" : "") << " = " << np << "\n";
   }
-  if (p.step == 2) blup_read(r, idx);   // prep_run (Pheno.cpp:1063-1068): samples without LOCO predictions are masked for the trait
+  if (p.step == 2 && !p.compute_corr) blup_read(r, idx);   // prep_run (Pheno.cpp:1063-1068): samples without LOCO predictions are masked for the trait
   int ncols = 1;
   std::vector<double> Xraw;  // col-major N x ncols
   if (!p.covar_file.empty()) {
@@ -734,7 +762,7 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
       const double v = r.Y[(size_t)q * N + i];
       if (v != MISSING) { total += v; if (r.ain[i]) { ns += 1.0; if (distinct.size() < 3) distinct.insert(v); } }
     }
-    if (distinct.size() <= 2 && !p.force_qt)  // Pheno.cpp:907-925
+    if (distinct.size() <= 2 && !p.force_qt && !p.compute_corr)  // Pheno.cpp:907-925
       throw std::runtime_error("phenotype '" + r.pheno_names[q] + "' has very few unique values (=" + std::to_string(distinct.size()) + "). If you really want to analyze it as a QT, use --force-qt.");
     for (int64_t i = 0; i < N; ++i) {
       double& v = r.Y[(size_t)q * N + i];
@@ -784,6 +812,7 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
   }
   // fit_null_logistic (Step1_Models.cpp:54-154): offsets of the covariate-only logistic model
   r.pheno_pass.assign(r.P, 1);
+  if (p.compute_corr) return;      // the LD matrix needs the samples and the covariate basis only
   if (p.bt) {
     sout << "   -fitting null logistic regression on binary phenotypes...";
     r.offset.assign((size_t)N * r.P, 0.0);

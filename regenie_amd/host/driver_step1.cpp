@@ -287,6 +287,10 @@ int run(int argc, char** argv) {
   }
   read_pheno_cov(r);
   sout << "   -phenotypes and covariates ready (" << since_start() << "ms since start)\n";
+  if (p.compute_corr) {
+    if (!run_ld_entry) throw std::runtime_error("--compute-corr is not part of this build of the driver.");
+    return run_ld_entry(r, t_start);
+  }
   if (p.step == 2) return run_step2_all(r, t_start);
   const int64_t N = r.N;
   const int P = r.P;

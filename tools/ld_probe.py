@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Times the LD-matrix library (include/rg_ld.h) on synthetic hard calls: append (upload, row store, covariate contraction) and finish
+(panel-pair Gram on the i8 matrix cores + fp64 epilogue + 16-bit quantisation), and prints the Gram kernel's integer operations per
+second.  With --driver DIR it also writes a .bed of the same size there and times `regenie-amd --step 2 --compute-corr` on it, and
+`oracle/_ref/regenie` on the same files when that binary exists (--ref-threads).
+
+  python tools/ld_probe.py --n 200000 --M 4096 [--miss 0.01] [--bsize 1024] [--driver DIR --ref-threads 16]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=200000)
+    ap.add_argument("--M", type=int, default=4096)
+    ap.add_argument("--C", type=int, default=3)
+    ap.add_argument("--miss", type=float, default=0.01)
+    ap.add_argument("--bsize", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--driver", default=None)
+    ap.add_argument("--ref-threads", type=int, default=16)
+    ap.add_argument("--ref-timeout", type=int, default=600)
+    a = ap.parse_args()
+    import torch
+    torch.cuda.init()
+    from regenie_amd.ld import R2_U16, LDMatrix
+    n, M, nb = a.n, a.M, (a.n + 3) // 4
+    rng = np.random.default_rng(1)
+    X = np.linalg.qr(np.column_stack([np.ones(n), rng.normal(size=(n, a.C - 1))]))[0]
+    g = torch.Generator(device="cuda").manual_seed(1)
+    panels = []
+    for p0 in range(0, M, a.bsize):
+        bs = min(a.bsize, M - p0)
+        maf = torch.rand((bs, 1), device="cuda", generator=g) * 0.48 + 0.02
+        u = torch.rand((bs, 4 * nb), device="cuda", generator=g)
+        gt = (u < maf * maf).to(torch.uint8) + (u < 1 - (1 - maf) ** 2).to(torch.uint8)
+        code = torch.where(gt == 2, 0, torch.where(gt == 1, 2, 3)).to(torch.uint8)
+        if a.miss > 0:
+            code[torch.rand((bs, 4 * nb), device="cuda", generator=g) < a.miss] = 1
+        code[:, n:] = 0
+        code = code.view(bs, nb, 4)
+        panels.append((code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)).contiguous().cpu().numpy())
+        del u, gt, code
+    res = {"n": n, "M": M, "C": a.C, "miss": a.miss, "bsize": a.bsize, "runs": []}
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        with LDMatrix(n, a.C, M) as ld:
+            ld.set_basis(X.T)
+            c0 = 0
+            for rows in panels:
+                ld.append(rows, np.arange(c0, c0 + rows.shape[0]))
+                c0 += rows.shape[0]
+            t1 = time.perf_counter()
+            ld.finish(R2_U16)
+            t2 = time.perf_counter()
+            ms, tiles = ld.kernel_ms, ld.tiles
+        ops = 2.0 * tiles * 128 * 128 * ((n + 63) // 64 * 64)
+        res["runs"].append({"append_s": t1 - t0, "finish_s": t2 - t1, "gram_ms": ms, "tiles": tiles, "gram_int_ops_per_s": ops / (ms * 1e-3)})
+    if a.driver:
+        os.makedirs(a.driver, exist_ok=True)
+        pre = os.path.join(a.driver, "ldprobe")
+        with open(pre + ".bed", "wb") as f:
+            f.write(bytes([0x6c, 0x1b, 0x01]))
+            for rows in panels:
+                f.write(rows.tobytes())
+        with open(pre + ".bim", "w") as f:
+            for j in range(M):
+                f.write("1\tv%d\t0\t%d\tA\tG\n" % (j + 1, j + 1))
+        with open(pre + ".fam", "w") as f:
+            for i in range(n):
+                f.write("%d %d 0 0 0 -9\n" % (i + 1, i + 1))
+        with open(pre + ".covar", "w") as f:
+            f.write("FID IID V1 V2\n")
+            cv = rng.normal(size=(n, 2))
+            for i in range(n):
+                f.write("%d %d %.5f %.5f\n" % (i + 1, i + 1, cv[i, 0], cv[i, 1]))
+        common = ["--step", "2", "--bed", pre, "--covarFile", pre + ".covar", "--bsize", str(a.bsize), "--compute-corr"]
+        t0 = time.perf_counter()
+        r = subprocess.run([os.path.join(ROOT, "regenie_amd", "bin", "regenie-amd")] + common + ["--out", pre + "_amd"], capture_output=True, text=True)
+        res["driver_wall_s"] = time.perf_counter() - t0
+        res["driver_rc"] = r.returncode
+        ref = os.path.join(ROOT, "oracle", "_ref", "regenie")
+        if os.path.exists(ref):
+            t0 = time.perf_counter()
+            try:
+                rr = subprocess.run([ref] + common + ["--threads", str(a.ref_threads), "--out", pre + "_ref"], capture_output=True, text=True, timeout=a.ref_timeout)
+                res["reference_wall_s"], res["reference_rc"] = time.perf_counter() - t0, rr.returncode
+                if rr.returncode == 0 and r.returncode == 0:
+                    x = np.fromfile(pre + "_amd.corr", np.uint16)
+                    y = np.fromfile(pre + "_ref.corr", np.uint16)
+                    res["values_differing_from_reference"] = int((x != y).sum()) if x.shape == y.shape else -1
+            except subprocess.TimeoutExpired:
+                res["reference_wall_s"] = "> %d (stopped)" % a.ref_timeout
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -328,6 +328,16 @@ int rg_k_chol_solve(void* stream, double* mats, int64_t mat_stride, int32_t batc
                     int32_t rhs_pad, int32_t nrhs /* valid RHS rows <= rhs_pad */,
                     double* dinv_ws /* batch*(T + 10*ceil(T/4))*4096 doubles, T = n_pad/64 */,
                     int32_t* info /* device int, set !=0 if not SPD */);
+/* The same factorization as level 0 runs it: systems formed from source matrices, right-hand sides embedded (the panel-of-128
+ * kernel, chol_p128.h).  System b = o * nshift + r is S[o] (- F[o] when F != NULL) + shift[r] I of order d_n[o] <= n_pad - embed
+ * (d_n, shift: device arrays); S[o], F[o]: n_pad x n_pad row-major, lower triangle, with `embed` right-hand sides in rows d_n[o] ..
+ * d_n[o] + embed - 1; n_pad a multiple of 128.  On exit mats[b] (n_pad x n_pad) holds L in the lower triangle of its first d_n[o] rows
+ * and, in the right-hand-side rows, y = L^-1 rhs (solve = 0) or x = A^-1 rhs (solve = 1); what lies past them is not written.
+ * dinv_ws as for rg_k_chol_solve (T = n_pad/64, batch = nouter * nshift): [batch][T][64 * 64] inverses of L's diagonal 64-tiles,
+ * then [batch][n_pad/128][128 * 128] inverses of its diagonal 128-blocks (16-blocks on and below the diagonal). */
+int rg_k_chol_solve_src(void* stream, const double* S, const double* F, const double* shift, int32_t nshift,
+                        const int32_t* d_n, int32_t nouter, int32_t n_pad, int32_t embed, int32_t solve,
+                        double* mats, double* dinv_ws, int32_t* info /* device int, set !=0 if not SPD */);
 /* C[m][n] = sum_k A[m][k]*B[n][k] (fp64 MFMA, row-major, K multiple of 64, m,n multiples of 64) */
 int rg_k_dgemm_nt(void* stream, const double* A, int64_t lda, const double* B, int64_t ldb,
                   int32_t m, int32_t n, int64_t k, double* C, int64_t ldc);

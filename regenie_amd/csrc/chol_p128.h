@@ -40,6 +40,8 @@
 // (hipcc computed the addresses of the LATER phases ahead of the K loop and spilled the K loop's own operands to scratch -- with an
 // s_waitcnt vmcnt in front of every reload, i.e. behind the stage copies just issued)
 #define C128_LAUNDER(x) asm volatile("" : "+v"(x))
+// between LDS accesses of ONE wave that hand values from lane to lane: the wave's LDS instructions execute in order, so nothing is waited for
+#define C128_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
 // end of a K stage: the products must have been issued before the wave waits for the next stage's copies (hipcc sank half of them below the barrier)
 #define C128_STAGE_SYNC_ACC(acc)                                                                                                        \
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier"                                                                            \
@@ -57,6 +59,10 @@
                : "memory")
 #else
 #define C128_LAUNDER(x) ((void)0)
+// the host runs a wave's lanes one after the other, so there it is a real barrier of the wave.  This names two internals of the host
+// scaffolding, tests/hipcpu/hip/hip_runtime.h: the per-wave barrier objects Block::wave[] and bar_wait() -- the same pair that file's own
+// __shfl_down and the matrix instruction's stand-in (tests/hipcpu/chol128_host.cpp) are built on; if they are renamed, rename them here.
+#define C128_WAVE_SYNC() hipcpu::bar_wait(hipcpu::g_blk.wave[threadIdx.x >> 6])
 #define C128_LDS_BARRIER() __syncthreads()
 #define C128_STAGE_SYNC_ACC(acc) C128_STAGE_SYNC()
 #define C128_STAGE_SYNC_ACCD(acc) C128_STAGE_SYNC()
@@ -89,7 +95,9 @@ __device__ __forceinline__ void c128_wait_upto(int n) {   // s_waitcnt vmcnt(4 *
 
 struct C128Args {
   double* mats; int64_t mat_stride; int n64;
-  double* linv;         // [batch][Tp][128 * 128]: inverse of the diagonal block of a panel, row-major
+  double* linv;         // [batch][Tp][128 * 128]: inverse of the diagonal block of a panel, row-major.  Only its 16 x 16 blocks on and below the
+                        // diagonal are ever written (the diagonal ones whole, zeros above the diagonal); the blocks above hold whatever the
+                        // workspace held.  The one reader, the triangular multiply below, copies them into LDS but never uses them (n <= cb).
   double* dinv;         // [batch][n64 / 64][64 * 64]: tile inverses for the back substitution (k_chol_backsolve*)
   int32_t* info;
   int j, Tp, batch, R, nplain;
@@ -123,7 +131,7 @@ struct C128Args {
 #define C128_T0() 0ull
 #endif
 
-// ---- blocked (16) factorization + inverse of the 64x64 tile held in LDS (diag_factor_lds of chol_common.h with a straight-line 16 x 16 step) ----
+// ---- blocked (16) factorization + inverse of the 64x64 tile held in LDS (diag_factor_lds of chol_common.h with the 16 x 16 step as 4 x 4 blocks on all of wave 0) ----
 // On return: lower triangle + diagonal of s = L, strict upper triangle = Linv^T, dv[r] = Linv[r][r].
 // Returns true (in some thread) when a pivot was not positive.
 __device__ __forceinline__ bool c128_factor64(double (&s)[CT][CT + 2], double (&dv)[CT], unsigned long long* dbg = nullptr) {
@@ -148,50 +156,89 @@ __device__ __forceinline__ bool c128_factor64(double (&s)[CT][CT + 2], double (&
   for (int sb = 0; sb < 4; ++sb) {
     const int o = sb * 16;
     const int nb = 3 - sb;   // 16-row blocks below the diagonal block
-    // (i) diagonal block: lanes 0..15 of wave 0 hold one row each in registers; then its inverse, one column each
-    if (tid < 16) {
-      // Straight-line code (round 6): the entries above the diagonal of the 16 x 16 block are don't-cares, so every update runs in all 16
-      // lanes without an exec mask per statement, a bad pivot is flagged without a branch, and the inverse is accumulated right-looking
-      // (16 independent chains instead of one dependent chain of r multiply-adds per entry): 13 instead of 32 us per tile.
-      // Cross-lane values are broadcast with v_readlane (compile-time lane index, no LDS round trip); square root and reciprocal come from
-      // one v_rsq_f64 + two Newton steps (~1 ulp).
-      double a[16], rdv[16];
+    // (i) diagonal block and its inverse on the 64 lanes of wave 0, as 4 x 4 blocks of 4 (second pass; before it lanes 0..15 held one row
+    // each: 16 dependent columns of up to 15 v_readlane / FMA pairs, then 16 more for the inverse -- 5.4 us per step, 68 % of this function).
+    // Lane (li, lq) holds A[li][lq + 4 r] in c[r] (the block is symmetric: the element D[lq + 4 r][li] of the matrix instruction) and
+    // T[lq + 4 r][li] in t[r], T = I - L Linv so far.  Per block column kb:
+    //   * every lane reads its row's four entries of the column and the 4 x 4 pivot block from LDS and factors that block itself (four
+    //     rsq + Newton chains, the same arithmetic in every lane: no cross-lane traffic), then solves its own row against it: x[k] = L[li][4 kb + k];
+    //   * lane (li, lq) keeps xs = x[lq]: exactly the A and the B operand of ONE v_mfma_f64_16x16x4 that applies the rank-4 update to all of c;
+    //   * the next block column goes back through LDS (the wave's own writes: no barrier), since a row's four entries sit in four lanes;
+    //   * the inverse rides along: lane column lq of the inverse W of the pivot block by forward substitution, Linv rows 4 kb .. + 3 =
+    //     W T[4 kb ..][.] and T -= L[.][4 kb ..] Linv[4 kb ..][.], one matrix instruction each.
+    // Entries above the diagonal are don't-cares throughout (they reach only results that are never stored); a bad pivot is flagged without
+    // a branch; square root and reciprocal come from one v_rsq_f64 + two Newton steps (~1 ulp).
+    if (wave == 0) {
+      v4d c, t;
 #pragma unroll
-      for (int c = 0; c < 16; ++c) a[c] = s[o + tid][o + c];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const double p0 = bcast_lane(a[c], c);
-        const bool ok = p0 > 0.0;
-        bad |= !ok;
-        const double piv = ok ? p0 : 1.0;
-        double r0 = __builtin_amdgcn_rsq(piv);
-        r0 = r0 * fma(-0.5 * piv * r0, r0, 1.5);
-        r0 = r0 * fma(-0.5 * piv * r0, r0, 1.5);
-        double d = piv * r0;
-        d = fma(0.5 * r0, fma(-d, d, piv), d);     // sqrt(piv)
-        const double rd = fma(r0, fma(-d, r0, 1.0), r0);        // 1 / sqrt(piv)
-        rdv[c] = rd;
-        a[c] = tid == c ? d : a[c] * rd;
-#pragma unroll
-        for (int c2 = c + 1; c2 < 16; ++c2) a[c2] = fma(-a[c], bcast_lane(a[c], c2), a[c2]);      // L[c2][c] from lane c2
+      for (int r = 0; r < 4; ++r) {
+        c[r] = s[o + li][o + lq + 4 * r];
+        t[r] = (lq + 4 * r == li) ? 1.0 : 0.0;
       }
 #pragma unroll
-      for (int c = 0; c < 16; ++c)
-        if (c <= tid) s[o + tid][o + c] = a[c];
-      // inverse of the 16x16 triangle, lane = column: x[j] = v[j] / L[j][j], then v[r] -= L[r][j] x[j] for the rows below
-      double v[16];
+      for (int kb = 0; kb < 4; ++kb) {
+        const int p = o + 4 * kb;
+        if (kb > 0 && li >= 4 * kb + lq) s[o + li][p + lq] = c[kb];      // this column's entries after the updates so far
+        C128_WAVE_SYNC();
+        double rv[4], g[4][4], d[4], rd[4], x[4];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = (r == tid) ? 1.0 : 0.0;
+        for (int k = 0; k < 4; ++k) rv[k] = s[o + li][p + k];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        v[j] *= rdv[j];
+        for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int r = j + 1; r < 16; ++r) v[r] = fma(-bcast_lane(a[j], r), v[j], v[r]);      // L[r][j] from lane r
+          for (int k = 0; k <= r; ++k) g[r][k] = s[p + r][p + k];
+        C128_WAVE_SYNC();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const double p0 = g[k][k];
+          const bool ok = p0 > 0.0;
+          bad |= !ok;
+          const double piv = ok ? p0 : 1.0;
+          double r0 = __builtin_amdgcn_rsq(piv);
+          r0 = r0 * fma(-0.5 * piv * r0, r0, 1.5);
+          r0 = r0 * fma(-0.5 * piv * r0, r0, 1.5);
+          double dd = piv * r0;
+          dd = fma(0.5 * r0, fma(-dd, dd, piv), dd);     // sqrt(piv)
+          d[k] = dd;
+          rd[k] = fma(r0, fma(-dd, r0, 1.0), r0);        // 1 / sqrt(piv)
+#pragma unroll
+          for (int r = k + 1; r < 4; ++r) g[r][k] *= rd[k];      // L[r][k] of the pivot block
+#pragma unroll
+          for (int r = k + 1; r < 4; ++r)
+#pragma unroll
+            for (int k2 = k + 1; k2 <= r; ++k2) g[r][k2] = fma(-g[r][k], g[k2][k], g[r][k2]);
+        }
+        // this lane's row against the pivot block (a row of the block itself: L up to its diagonal, which takes the square root as computed)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          double v = rv[k];
+#pragma unroll
+          for (int k2 = 0; k2 < k; ++k2) v = fma(-x[k2], g[k][k2], v);
+          x[k] = (li == 4 * kb + k) ? d[k] : v * rd[k];
+        }
+        const double xs = lq == 0 ? x[0] : (lq == 1 ? x[1] : (lq == 2 ? x[2] : x[3]));      // L[li][4 kb + lq]
+        if (li >= 4 * kb + lq) s[o + li][p + lq] = xs;
+        if (kb < 3) c = __builtin_amdgcn_mfma_f64_16x16x4f64(-xs, xs, c, 0, 0, 0);
+        // column lq of W = inverse of the pivot block: w[j] = W[j][lq]
+        double w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = (j == lq) ? 1.0 : 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          w[j] *= rd[j];
+#pragma unroll
+          for (int r = j + 1; r < 4; ++r) w[r] = fma(-g[r][j], w[j], w[r]);
+        }
+        const int lr = li & 3;
+        double ws = lr == 0 ? w[0] : (lr == 1 ? w[1] : (lr == 2 ? w[2] : w[3]));
+        ws = (li >> 2) == kb ? ws : 0.0;                   // A[li][lq] = W[li - 4 kb][lq] on the rows of this block column, 0 elsewhere
+        const v4d xr = __builtin_amdgcn_mfma_f64_16x16x4f64(ws, t[kb], (v4d){0, 0, 0, 0}, 0, 0, 0);
+        const double iv = xr[kb];                          // Linv[4 kb + lq][li]
+        const int ir = 4 * kb + lq;
+        if (ir == li) dv[o + li] = iv;
+        if (ir > li) s[o + li][o + ir] = iv;               // transposed into the upper triangle
+        if (kb < 3) t = __builtin_amdgcn_mfma_f64_16x16x4f64(-xs, iv, t, 0, 0, 0);
       }
-      dv[o + tid] = v[tid];
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (r > tid) s[o + tid][o + r] = v[r];   // Linv[r][tid], transposed into the upper triangle
     }
     C128_FT(11);
     C128_LDS_BARRIER();
@@ -497,7 +544,7 @@ __global__ __launch_bounds__(256, 2) void k_c128_panel(C128Args a) {
         out[1] = (v4d){0, 0, 0, 0};
 #pragma unroll
         for (int n = 0; n < 8; ++n) {
-          if (n > cb || (a.flags & 4)) continue;
+          if (n > cb || (a.flags & 4)) continue;      // column blocks n > cb of the unit are not data: linv is never written there
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const double lv = c128_rows16_at(cur, n, r, i, q);
@@ -637,7 +684,7 @@ __global__ __launch_bounds__(256, 2) void k_c128_panel(C128Args a) {
       const int r = e >> 6, c = e & 63;
       if (c <= r) Dg[(int64_t)(o + r) * n64 + o + c] = sA[r][c];
       const double lv = (c < r) ? sA[c][r] : (c == r ? dv[r] : 0.0);
-      Lv[(o + r) * 128 + o + c] = lv;
+      if (c < ((r >> 4) + 1) * 16) Lv[(o + r) * 128 + o + c] = lv;      // the triangular multiply uses row block cb up to column 16 (cb + 1) only (C128Args::linv)
       Iv[(int64_t)t * CT * CT + e] = lv;
     }
   };
@@ -752,7 +799,9 @@ static void c128_launch_factor(hipStream_t st, double* mats, int64_t mat_stride,
   a.Tp = n64 / 128; a.batch = batch; a.R = R; a.fs = first;
   static const bool dbg = getenv("RG_C128_DBG") && atoi(getenv("RG_C128_DBG")) != 0;
   a.dbg = nullptr;
-  if (dbg && hipMalloc(&a.dbg, (64 + 2048) * sizeof(unsigned long long)) == hipSuccess) {
+  // (the per-launch entries [20 ..], [32 ..], [44 ..] hold 12 launches each and the kernel indexes them by j: no diagnostic for larger orders)
+  if (dbg && a.Tp > 12) fprintf(stderr, "c128 phases: not collected for n64 %d (more than 12 panels)\n", n64);
+  if (dbg && a.Tp <= 12 && hipMalloc(&a.dbg, (64 + 2048) * sizeof(unsigned long long)) == hipSuccess) {
     (void)hipMemsetAsync(a.dbg, 0, (64 + 2048) * sizeof(unsigned long long), st);
     (void)hipMemsetAsync(a.dbg + 32, 0xFF, 12 * sizeof(unsigned long long), st);      // [32 + launch]: earliest workgroup start, [44 + launch]: latest end
   }

@@ -902,6 +902,17 @@ int rg_k_chol_solve(void* stream, double* mats, int64_t mat_stride, int32_t batc
   return hipGetLastError() == hipSuccess ? RG_OK : RG_ERR_HIP;
 }
 
+int rg_k_chol_solve_src(void* stream, const double* S, const double* F, const double* shift, int32_t nshift, const int32_t* d_n,
+                        int32_t nouter, int32_t n_pad, int32_t embed, int32_t solve, double* mats, double* dinv_ws, int32_t* info) {
+  if (!S || !shift || !d_n || !mats || !dinv_ws || !info || nshift < 1 || nouter < 1 || n_pad < 128 || (n_pad & 127) || embed < 0 ||
+      (solve && embed < 1)) return RG_ERR_ARG;
+  const int64_t msz = (int64_t)n_pad * n_pad;
+  // level 0's own call (rg_l0_blocks): group-wise path, right-hand sides embedded below each system's order -> the panel-of-128 kernel
+  rg_launch_chol_solve_formed_x((hipStream_t)stream, S, msz, F, msz, 1, shift, nshift, d_n, n_pad, nouter, mats, msz, n_pad, 0,
+                                solve ? embed : 0, dinv_ws, info, nullptr, F ? 1 : 0, nullptr, 0, 0, 1, 0, -1, 0, embed);
+  return hipGetLastError() == hipSuccess ? RG_OK : RG_ERR_HIP;
+}
+
 int rg_k_dgemm_nt(void* stream, const double* A, int64_t lda, const double* B, int64_t ldb, int32_t m,
                   int32_t n, int64_t k, double* C, int64_t ldc) {
   if (!A || !B || !C || (m & 63) || (n & 63) || (k & 63) || m < 64 || n < 64 || k < 64) return RG_ERR_ARG;

@@ -58,7 +58,7 @@ class RgTiming(C.Structure):
 EXPORTS = ["rg_create", "rg_destroy", "rg_last_error", "rg_set_problem", "rg_set_l0_workspace", "rg_w_rows", "rg_w_bytes",
            "rg_set_w_buffer", "rg_set_block_range", "rg_w_device_ptr", "rg_l0_blocks", "rg_l0_blocks_f64", "rg_sync", "rg_l0_get_w",
            "rg_l0_set_w", "rg_l1_qt", "rg_l1_qt_loocv", "rg_l1_bt", "rg_l1_cox", "rg_set_collective", "rg_set_l1_view", "rg_set_loco_output", "rg_enable_timing", "rg_get_timing", "rg_k_gram_i8", "rg_k_gram_fp4",
-           "rg_k_chol_solve", "rg_k_dgemm_nt", "rg_k_xy_i8", "rg_k_wgram", "rg_k_mfma_peak",
+           "rg_k_chol_solve", "rg_k_chol_solve_src", "rg_k_dgemm_nt", "rg_k_xy_i8", "rg_k_wgram", "rg_k_mfma_peak",
            # one node, several GPUs: level-0 hand-off over RCCL / peer copies; streamed ingest helpers (used by the C++ driver)
            "rg_group_create", "rg_group_destroy", "rg_l0_finish", "rg_group_prepare", "rg_group_abort", "rg_l0_batch_blocks", "rg_host_alloc", "rg_host_free", "rg_host_register", "rg_host_unregister",
            "rg_ingest_fence", "rg_stage_alloc", "rg_stage_copy", "rg_stage_free", "rg_stage_fits",
@@ -147,6 +147,8 @@ def load_library() -> C.CDLL:
                                   C.c_int64, C.c_void_p, C.c_int64]
     lib.rg_k_chol_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rg_k_chol_solve_src.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rg_k_dgemm_nt.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                   C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64]
     lib.rg_k_xy_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

@@ -18,7 +18,8 @@
 //   driver_common.cpp  text helpers, the option table (Regenie.cpp:146-371 subset), small utilities
 //   driver_models.cpp  covariate-only null models and the host-side statistics (logistic / Poisson / Cox null fits, Firth, p-values)
 //   driver_inputs.cpp  genotype metadata (.bim/.fam, .pvar/.psam, .bgen), phenotype / covariate files, LOCO files, the level-0 job files
-//   driver_step2.cpp   `--step 2`: single-variant tests on the rg_step2.h kernels, one part per GPU
+//   driver_step2.cpp   `--step 2`: single-variant tests on the rg_step2.h kernels, one part per GPU (driver_step2.h: what it shares with the next)
+//   driver_step2_bgen.cpp  the BGEN read-ahead of `--step 2` (BgenAhead), the planning of its groups
 //   driver_ld.cpp      `--step 2 --compute-corr`: the LD matrix of a region on the rg_ld.h kernels
 //   driver_step1.cpp   `--step 1`: streamed ingest, level 0, the multi-GPU exchange, level 1, the .loco / .prs writers; run()
 //   driver_main.cpp    main()

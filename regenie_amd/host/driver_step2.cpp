@@ -1,141 +1,70 @@
 // regenie-amd, the C++ host driver (see driver.h): `--step 2`.
-#include "driver.h"
-#include <functional>
+#include "driver_step2.h"
 
 namespace rgdrv {
 
 // The per-variant corrections -- fit_firth_logistic_snp_fast (Step2_Models.cpp:1158-1253) and run_SPA_test_snp (:2072-2297) -- run on the
 // device behind the C ABI (rg_s2_bt_correct, regenie_amd/csrc/step2_bt.hip).
 
-// One part of a `--step 2` run: the blocks [blk_lo, blk_hi) of the run's block list (chromosomes in file order, ceil(n_chr / bsize) blocks
-// each) on one device.  A run on G GPUs is G parts on G host threads -- the blocks are independent, there is no exchange -- whose result
-// lines go to part files that are concatenated in block order afterwards (run_step2_all).
-struct S2Part {
-  int part = 0, nparts = 1, device = 0;
-  int blk_lo = 0, blk_hi = INT_MAX;
-  int64_t n_ignored_snps = 0, n_ignored_tests = 0;     // out
-  std::vector<std::string> firth_body;                 // out: --write-null-firth lines per trait
-  std::vector<std::string> files;                      // out: the part's result files, one per trait
-};
+// buildLookupTable (Geno.cpp:2833-2856): 00 -> 2, 01 -> missing (-3), 10 -> 1, 11 -> 0 copies of the first .bim allele
+static const double lut[4] = {2.0, -3.0, 1.0, 0.0};
 
-int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& part) {
-  const Params& p = r.p;
-  const int64_t N = r.N;
-  const int P = r.P, C = r.C;
-  std::vector<int64_t> an;                      // analysed samples (rows handed to the device), file order
+S2Common::S2Common(Run& r_, const S2Part& part_) : r(r_), p(r_.p), part(part_), N(r_.N), P(r_.P), C(r_.C) {
   for (int64_t i = 0; i < N; ++i) if (r.ain[i]) an.push_back(i);
-  const int64_t n = (int64_t)an.size();
-  bool any_missing = false;                     // filters->has_missing: a sample masked for at least one trait
-  std::vector<uint8_t> has_missing(n, 0);
+  n = (int64_t)an.size();
+  has_missing.assign(n, 0);
   for (int64_t k = 0; k < n; ++k)
     for (int q = 0; q < P; ++q)
       if (!r.mask[(size_t)q * N + an[k]]) { has_missing[k] = 1; any_missing = true; }
-  const bool dense_route = getenv("RG_S2_DENSE") != nullptr;     // the fp64 route of the library (rg_s2_qt_block), kept for comparison
-  const bool glm = p.bt || p.ct;                                 // binary / count traits: the score test of a generalised linear null model
-  // compact, sample-fastest copies for the C ABI
-  std::vector<double> Xc((size_t)C * n), Yc((size_t)P * n), resc((size_t)P * n), scf(P);
-  std::vector<uint8_t> Mc((size_t)P * n);
+  glm = p.bt || p.ct;                                 // binary / count traits: the score test of a generalised linear null model
+  Xc.resize((size_t)C * n); Yc.resize((size_t)P * n); Mc.resize((size_t)P * n);
   for (int c = 0; c < C; ++c) for (int64_t k = 0; k < n; ++k) Xc[(size_t)c * n + k] = r.X[(size_t)c * N + an[k]];
   for (int q = 0; q < P; ++q)
     for (int64_t k = 0; k < n; ++k) { Yc[(size_t)q * n + k] = (glm ? r.Yraw : r.Y)[(size_t)q * N + an[k]]; Mc[(size_t)q * n + k] = r.mask[(size_t)q * N + an[k]]; }
-  // binary traits (compute_res_bin, Data.cpp:2439-2445; compute_score_bt, Step2_Models.cpp:471-552): per chromosome the null logistic
-  // model with the LOCO offset gives p^, w = p^ (1 - p^); the score test of a variant needs, per trait, sum w g~^2, X^T W g~ and
-  // g~ . (y - p^) -- contractions of the hard-call row with fixed columns, which rg_s2_contract_packed evaluates on the i8 matrix cores
-  std::vector<double> bt_fit, bt_vstat;
-  std::vector<int32_t> bt_counts;
-  std::vector<uint8_t> bt_pass(P, 1), test_ignored;
-  const bool firth = p.bt && p.firth, spa = p.bt && p.spa, correct = firth || spa;
-  const double z_thr = correct ? norm_quantile(1.0 - 0.5 * p.pthresh) : 0.0;   // sqrt of the chi-square(1) quantile at 1 - pThresh (Data.cpp:2119-2120)
-  std::vector<double> firth_off;                      // [P][n] cov_blup_offset: X beta_nullFirth + LOCO prediction (fit_null_firth, Step2_Models.cpp:1011-1013)
-  if (firth) firth_off.assign((size_t)P * n, 0.0);
-  std::vector<double> firth_bnull((size_t)P * C, 0.0), blup_off;      // exact Firth: the covariate-only estimates (start values), the LOCO offsets
-  std::vector<std::string> null_firth_files, firth_file_body(P);       // --use-null-firth: per-trait files of the list; --write-null-firth: what goes out
-  if (!p.use_null_firth.empty()) {      // check_firth_file / the list reader (Step2_Models.cpp:1871-1934): `<phenotype> <file>` per line
-    sout << " * reading null Firth estimates using file : [" << p.use_null_firth << "]\n";
-    null_firth_files.assign(P, "");
-    TextIn lf(p.use_null_firth);
-    if (!lf) throw std::runtime_error("cannot read file : " + p.use_null_firth);
-    std::string ln;
-    while (std::getline(lf, ln)) {
-      const auto t = split_ws(ln);
-      if (t.empty()) continue;
-      if (t.size() != 2) throw std::runtime_error("incorrectly formatted file specified by --use-null-firth.");
-      for (int q = 0; q < P; ++q) if (r.pheno_names[q] == t[0]) null_firth_files[q] = t[1];
-    }
-  }
-  if (p.write_null_firth) sout << " * writing null Firth estimates to file\n";
-  if (firth && !p.firth_approx) blup_off.assign((size_t)P * n, 0.0);
-  std::vector<double> denum_v;                        // per (variant, trait): the score test's denominator
-  std::vector<uint8_t> corrected, corr_fail;          // per (variant, trait) of a block
-  std::vector<double> corr_beta, corr_se, corr_chisq, corr_logp;
-  if (glm) bt_fit.assign((size_t)P * n, 0.5);
-
-  rg_s2_ctx* s2 = nullptr;
-  if (rg_s2_create(&s2, part.device, n, C, P) != RG_S2_OK || !s2) throw std::runtime_error("no MI355X / HIP device available (rg_s2_create failed)");
-  auto s2check = [&](int rc) { if (rc != RG_S2_OK) throw std::runtime_error(rg_s2_last_error(s2)); };
-  enum class In { Bed, PgenHard, Dosage };
-  const In in = r.dosage_mode ? In::Dosage : (r.pgen ? In::PgenHard : In::Bed);
-  const bool show_info = r.dosage_mode;                 // params.dosage_mode: the INFO column
-  const int flip = (in == In::Bed && p.ref_first) ? 1 : 0;   // .pgen rows always count ALT (PgenReader::Read / ReadHardcalls)
-  // check_sparse_G: params.n_samples, params.prop_zero_thr (Regenie.hpp:311); the .pgen reader counts the observed zeros itself
-  s2check(rg_s2_set_sparse_rule(s2, N, 0.5, r.pgen ? 1 : 0));
-
-  // blocks per chromosome (set_blocks_for_testing: ceil(n_chr / bsize))
-  std::map<int, std::vector<int64_t>> chr_snps;
+  firth = p.bt && p.firth; spa = p.bt && p.spa; correct = firth || spa;
+  z_thr = correct ? norm_quantile(1.0 - 0.5 * p.pthresh) : 0.0;   // sqrt of the chi-square(1) quantile at 1 - pThresh (Data.cpp:2119-2120)
+  per_trait = any_missing || glm;
+  in = r.dosage_mode ? In::Dosage : (r.pgen ? In::PgenHard : In::Bed);
+  show_info = r.dosage_mode;                            // params.dosage_mode: the INFO column
+  flip = (in == In::Bed && p.ref_first) ? 1 : 0;        // .pgen rows always count ALT (PgenReader::Read / ReadHardcalls)
+  dscale = r.bgenh ? 255 : 16384;
+  multi = part.nparts > 1;                              // parts write plain part files; run_step2_all concatenates (and compresses) them
   for (size_t j = 0; j < r.snp_chrom.size(); ++j) chr_snps[r.snp_chrom[j]].push_back((int64_t)j);
-  // in_non_par (Geno.cpp:2419, :2251): outside the pseudo-autosomal regions of chromosome X the reference halves the males' calls in the
-  // MAC (and, with the default dosage compensation off, nothing else) -- with no male in the sample file that is the autosomal rule
-  if (chr_snps.count(p.nchrom) && r.has_male)
-    throw std::runtime_error("--step 2 on chromosome " + std::to_string(p.nchrom) + " (X) with male samples: the sex-aware allele counts of the non-PAR region "
-                             "are not built; test the autosomes (or supply a sample file without sex codes of 1).");
-  int total_blocks = 0;
   for (auto& kv : chr_snps) total_blocks += (int)((kv.second.size() + p.bsize - 1) / p.bsize);
-  sout << std::left << std::setw(20) << " * block size" << ": [" << p.bsize << "]\n";
-  sout << std::left << std::setw(20) << " * # blocks" << ": [" << total_blocks << "]\n";
-  sout << " * approximate memory usage : n/a (genotype blocks are tested on the GPU)\n";
-  sout << " * using minimum MAC of " << p.min_mac << " (variants with lower MAC are ignored)\n";
-
-  // output files, one per phenotype (split_by_pheno is the default; print_header_output_single, Step2_Models.cpp:2386-2398)
-  std::vector<std::unique_ptr<TextOut>> ofs;
-  std::vector<std::string> out_names;
-  const bool multi = part.nparts > 1;        // parts write plain part files; run_step2_all concatenates (and compresses) them
-  for (int q = 0; q < P; ++q) {
-    out_names.push_back(p.out + "_" + r.pheno_names[q] + ".regenie" + (multi ? ".part" + std::to_string(part.part) : (p.gz ? ".gz" : "")));
-    ofs.emplace_back(new TextOut(out_names.back(), multi ? false : p.gz));
-    if (!*ofs.back()) throw std::runtime_error("cannot write file : " + out_names.back());
-    if (part.part == 0) *ofs.back() << "CHROM GENPOS ID ALLELE0 ALLELE1 A1FREQ " << (show_info ? "INFO " : "") << "N TEST BETA SE CHISQ LOG10P EXTRA\n";
+  file_idx.assign(n, 0);
+  int64_t kept = 0, k = 0;
+  for (int64_t i = 0; i < r.n_file && k < n; ++i) {
+    if (r.ind_ignore[i]) continue;
+    if (kept == an[k]) file_idx[k++] = i;
+    ++kept;
   }
-  part.files = out_names;
-
-  const int fd = in == In::Bed ? open((p.bed + ".bed").c_str(), O_RDONLY) : -1;
-  if (in == In::Bed && fd < 0) throw std::runtime_error("cannot read bed file");
-  std::vector<int64_t> file_idx(n, 0);          // file index of every analysed sample
-  {
-    int64_t kept = 0, k = 0;
-    for (int64_t i = 0; i < r.n_file && k < n; ++i) {
-      if (r.ind_ignore[i]) continue;
-      if (kept == an[k]) file_idx[k++] = i;
-      ++kept;
-    }
-  }
-  int nthreads = p.threads > 0 ? p.threads : std::max(1, usable_cpus() - 1);   // Regenie.cpp:1104-1106
-  nthreads = std::max(1, std::min(nthreads, 64) / part.nparts);
-  // buildLookupTable (Geno.cpp:2833-2856): 00 -> 2, 01 -> missing (-3), 10 -> 1, 11 -> 0 copies of the first .bim allele
-  static const double lut[4] = {2.0, -3.0, 1.0, 0.0};
-  std::vector<uint8_t> rows, packed;
-  std::vector<double> G, stats, bhat, sfac, mean_v, totp_v, dbuf, ibuf;
-  std::vector<int32_t> ign, nobs_v, nobsp_v;
-  std::vector<int64_t> vidx;
-  std::vector<uint16_t> G16;
-  bool identity = n == r.n_file;                 // every sample of the file is analysed, in file order
+  identity = n == r.n_file;
   for (int64_t k = 0; identity && k < n; ++k) identity = file_idx[k] == k;
-  int64_t n_ignored_snps = 0, n_ignored_tests = 0, n_tested = 0;
-  int block = 0;
-  // .bed rows of a block: runs of consecutive variants are cut into pieces read by several threads (the page-cache copy of one pread is a
-  // single core's memcpy), and the NEXT block of the chromosome is read while the current one is tested
-  std::vector<uint8_t> rows_ahead;
-  std::future<void> ahead;
-  auto read_bed = [&](const std::vector<int64_t>& snps, int64_t j0, int bs, std::vector<uint8_t>& buf) {
+  nthreads = p.threads > 0 ? p.threads : std::max(1, usable_cpus() - 1);   // Regenie.cpp:1104-1106
+  nthreads = std::max(1, std::min(nthreads, 64) / part.nparts);
+  // host threads of the BGEN read-ahead: inflate is the bound of this input (about 10 ms per 1.5 MB block and thread with zlib), so it takes
+  // --threads as given, or every hardware thread but two, shared by the parts of a multi-GPU run
+  nt_prep = env.prep_threads ? env.prep_threads : std::max(1, std::min(p.threads > 0 ? p.threads : usable_cpus(), 256) / part.nparts);
+  ld16 = (n + 7) / 8 * 8;
+  fast_bgen = in == In::Dosage && r.bgenh && (!env.dense || glm) && !(correct && !spa && !p.firth_approx) && !env.bgen_rows;
+}
+
+// .bed rows of a block: runs of consecutive variants are cut into pieces read by several threads (the page-cache copy of one pread is a
+// single core's memcpy), and the NEXT block of the chromosome is read while the current one is tested
+class BedAhead {
+ public:
+  explicit BedAhead(const S2Common& cm) : cm_(cm), fd_(open((cm.p.bed + ".bed").c_str(), O_RDONLY)) { if (fd_ < 0) throw std::runtime_error("cannot read bed file"); }
+  ~BedAhead() { if (ahead_.valid()) ahead_.wait(); close(fd_); }
+  // the block's rows: read ahead by the previous call when it could be (same chromosome), else read now; then (bn > 0) the next block is started
+  const uint8_t* take(const std::vector<int64_t>& snps, int64_t j0, int bs, int bn) {
+    if (ahead_.valid()) { ahead_.get(); rows_.swap(rows_ahead_); }
+    else read_bed(snps, j0, bs, rows_);
+    if (bn > 0) ahead_ = std::async(std::launch::async, [this, &snps, jn = j0 + bs, bn]() { read_bed(snps, jn, bn, rows_ahead_); });
+    return rows_.data();
+  }
+ private:
+  void read_bed(const std::vector<int64_t>& snps, int64_t j0, int bs, std::vector<uint8_t>& buf) {
+    const Run& r = cm_.r;
     buf.resize((size_t)bs * r.bpr);
     struct Piece { int64_t file_off, buf_off, len; };
     std::vector<Piece> pieces;
@@ -148,324 +77,65 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
       j = e;
     }
     std::atomic<int> failed(0);
-    parallel_for((int)pieces.size(), std::min(nthreads, 8), [&](int t) {
+    parallel_for((int)pieces.size(), std::min(cm_.nthreads, 8), [&](int t) {
       int64_t got = 0;
       while (got < pieces[t].len) {
-        const ssize_t k = pread(fd, buf.data() + pieces[t].buf_off + got, (size_t)(pieces[t].len - got), pieces[t].file_off + got);
+        const ssize_t k = pread(fd_, buf.data() + pieces[t].buf_off + got, (size_t)(pieces[t].len - got), pieces[t].file_off + got);
         if (k <= 0) { failed = 1; return; }
         got += k;
       }
     });
     if (failed) throw std::runtime_error("cannot read bed file");
-  };
-  // 8-bit .bgen blocks (the UK Biobank encoding): the host threads inflate the NEXT block of this part and walk its bytes once -- 2-byte
-  // integer dosages (units of 1 / 255) into a pinned buffer, the allele / info sums of parseSnpfromBGEN (Geno.cpp:2186-2330) in the
-  // reference's order -- while the device tests the current block and its result lines are formatted.  The three double rows per variant
-  // of the general route (dosage, info term, analysed-sample copy: 12 MB per variant at 500,000 samples) do not exist on this one.
-  struct DosPrep {
-    uint16_t* g16 = nullptr;                 // pinned, bsize rows of ld16 entries
-    std::vector<uint8_t> raw, ignored;
-    std::vector<double> total, info_num, af_t, info_t;
-    std::vector<int64_t> ns1, ns_t;
-    bool integral = false;
-    double ms_inflate = 0, ms_walk = 0, ms_wall = 0;
-    std::string err;
-    // device route (csrc/bgen_inflate.hip): the stored zlib streams in page-locked memory, the dosage rows left in device memory
-    int64_t g16_rows = 0;                    // rows the pinned buffer holds (the host route's; allocated when that route is first taken)
-    uint8_t* comp = nullptr; int64_t comp_cap = 0;
-    const uint16_t* g16_dev = nullptr; int64_t ld_dev = 0;
-    int dev_rows = 0;                        // rows [0, dev_rows) of the group are in device memory (g16_dev), the others in g16 from row host_row0 on
-    int host_row0 = 0;
-    bool dev_bad = false;
-    double ms_read = 0, ms_dev = 0;
-    // the stored streams of the group that will be decoded into this slot NEXT, read while the other slot's group is decoded
-    std::vector<int64_t> rd_off; std::vector<int32_t> rd_clen, rd_ulen;
-    std::future<bool> rd; int64_t rd_group = -1; double rd_ms = 0;
-  };
-  const int64_t ld16 = (n + 7) / 8 * 8;
-  // host threads of the read-ahead: inflate is the bound of this input (about 10 ms per 1.5 MB block and thread with zlib), so it takes
-  // --threads as given, or every hardware thread but two, shared by the parts of a multi-GPU run
-  const int nt_prep = getenv("RG_S2_PREP_THREADS") ? std::max(1, atoi(getenv("RG_S2_PREP_THREADS")))
-                                                    : std::max(1, std::min(p.threads > 0 ? p.threads : usable_cpus(), 256) / part.nparts);
-  const bool fast_bgen = in == In::Dosage && r.bgenh && (!dense_route || glm) && !(correct && !spa && !p.firth_approx) && !getenv("RG_S2_BGEN_ROWS");
-  DosPrep preps[2];
-  // BGEN inflate + byte walk on the GPU (default for zlib files; RG_S2_BGEN_HOST=1 keeps the host threads' route, which also takes every
-  // block the device decoder flags: a damaged stream, another encoding).  The decoder has its own stream: it works on the next block while
-  // the scoring kernels of the current one run.
-  rg_bgen_dev* bdev = nullptr;
-  int64_t n_dev_blocks = 0, n_host_blocks = 0;
-  double ms_dev_read = 0, ms_dev_decode = 0;
-  struct BlkRef { const std::vector<int64_t>* snps; int64_t j0; int bs; };
-  std::vector<BlkRef> my_blocks;             // this part's blocks in the order they are tested
-  size_t my_next = 0;
-  int64_t bgen_block_bytes = 0;
-  double ms_chr = 0, ms_prep_wall = 0, ms_prep_wait = 0, ms_device = 0, ms_format = 0, ms_inflate = 0, ms_walk = 0;
-  if (fast_bgen) {
-    if (rg_bgen_block_bytes(r.bgenh, &bgen_block_bytes) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(r.bgenh));
-    bgen_block_bytes = (bgen_block_bytes + 63) / 64 * 64;
-    int32_t bcomp = 0;
-    rg_bgen_info(r.bgenh, nullptr, nullptr, &bcomp, nullptr);
-    if (bcomp == 1 && !getenv("RG_S2_BGEN_HOST") && rg_bgen_dev_create(&bdev, part.device) == RG_BGEN_OK) {
-      const bool per_trait = any_missing || glm;
-      if (rg_bgen_dev_set_samples(bdev, r.n_file, n, identity ? nullptr : file_idx.data(), per_trait ? P : 0, per_trait ? Mc.data() : nullptr) != RG_BGEN_OK) {
-        rg_bgen_dev_destroy(bdev);
-        bdev = nullptr;
-      }
-    }
-    int b = 0;
-    for (int chrom : r.chr_read) {
-      if (!chr_snps.count(chrom)) continue;
-      const std::vector<int64_t>& sn = chr_snps[chrom];
-      const int nbc = (int)((sn.size() + p.bsize - 1) / p.bsize);
-      for (int bb = 0; bb < nbc; ++bb, ++b)
-        if (b >= part.blk_lo && b < part.blk_hi)
-          my_blocks.push_back({&sn, (int64_t)bb * p.bsize, (int)std::min<int64_t>(p.bsize, (int64_t)sn.size() - (int64_t)bb * p.bsize)});
-    }
   }
-  // The device decoder works on one stream per wavefront and needs thousands of them in flight: the blocks of a chromosome are prepared in
-  // groups of >= RG_S2_BGEN_GROUP variants (default 3,072 = the streams the GPU holds at once) whatever --bsize is; the host route keeps
-  // one block per group.  A group is a range of the chromosome's variants, i.e. a BlkRef of its own.
-  struct Group { BlkRef ref; size_t first_block; int dev_rows; std::vector<int> starts; };
-  std::vector<Group> groups;
-  std::vector<std::pair<size_t, int>> block_group;      // per block of my_blocks: its group, its first row there
-  if (fast_bgen) {
-    // RG_S2_BGEN_HOST_SHARE=f: the host threads take the share f of every group beside the device (whole blocks from the group's end; their
-    // route gives the same result lines -- both are held to regenie's).  The device's part keeps its size -- a launch takes as long for 2,000
-    // streams as for 3,072, every stream being a chain of its own -- and the host's blocks come on top.  Off by default: on a box that gives
-    // the job 16 CPUs the workers take those from the reads, the chromosome set-ups and the uploads (36,864 variants at 500,000 samples: 4.3 s
-    // without, 4.7 s with f = 0.25, 5.4 s with 0.38, 6.9 s with 0.5); it is for hosts with idle cores.  The share is fixed for a run, so that
-    // the split does not depend on timing.
-    double share = 0.0;
-    if (bdev)
-      if (const char* e = getenv("RG_S2_BGEN_HOST_SHARE")) share = std::min(0.9, std::max(0.0, atof(e)));
-    const int dev_target = std::max(p.bsize, getenv("RG_S2_BGEN_GROUP") ? atoi(getenv("RG_S2_BGEN_GROUP")) : 3072);
-    const int target = bdev ? (int)std::min(65536.0, dev_target / (1.0 - share)) : p.bsize;
-    for (size_t b = 0; b < my_blocks.size(); ++b) {
-      const BlkRef& br = my_blocks[b];
-      if (!groups.empty()) {
-        Group& g = groups.back();
-        if (g.ref.snps == br.snps && g.ref.j0 + g.ref.bs == br.j0 && g.ref.bs + br.bs <= target) {
-          block_group.push_back({groups.size() - 1, g.ref.bs});
-          g.starts.push_back(g.ref.bs);
-          g.ref.bs += br.bs;
-          continue;
-        }
-      }
-      groups.push_back({br, b, 0, {0}});
-      block_group.push_back({groups.size() - 1, 0});
-    }
-    for (Group& g : groups) {
-      g.dev_rows = bdev ? g.ref.bs : 0;
-      if (bdev && share > 0.0) {      // the block boundary nearest to the device's share; a group of one block stays whole
-        const double want = (1.0 - share) * g.ref.bs;
-        int best = g.ref.bs;
-        for (int st : g.starts) if (st > 0 && std::fabs(st - want) < std::fabs(best - want)) best = st;
-        g.dev_rows = best;
+  const S2Common& cm_;
+  const int fd_;
+  std::vector<uint8_t> rows_, rows_ahead_;
+  std::future<void> ahead_;
+};
+
+// The null models of a chromosome.  Binary traits (compute_res_bin, Data.cpp:2439-2445; compute_score_bt, Step2_Models.cpp:471-552): the
+// null logistic model with the LOCO offset gives p^, w = p^ (1 - p^); the score test of a variant needs, per trait, sum w g~^2, X^T W g~
+// and g~ . (y - p^) -- contractions of the hard-call row with fixed columns, which rg_s2_contract_packed evaluates on the i8 matrix cores.
+struct ChromNull {
+  const S2Common& cm;
+  std::vector<double> bt_fit, resc, scf;
+  std::vector<uint8_t> bt_pass;
+  std::vector<double> firth_off;                      // [P][n] cov_blup_offset: X beta_nullFirth + LOCO prediction (fit_null_firth, Step2_Models.cpp:1011-1013)
+  std::vector<double> firth_bnull, blup_off;          // exact Firth: the covariate-only estimates (start values), the LOCO offsets
+  std::vector<std::string> null_firth_files, firth_file_body;       // --use-null-firth: per-trait files of the list; --write-null-firth: what goes out
+  double ms_chr = 0;
+
+  explicit ChromNull(const S2Common& cm_) : cm(cm_), resc((size_t)cm_.P * cm_.n), scf(cm_.P), bt_pass(cm_.P, 1), firth_bnull((size_t)cm_.P * cm_.C, 0.0), firth_file_body(cm_.P) {
+    const Params& p = cm.p;
+    const int P = cm.P;
+    if (cm.firth) firth_off.assign((size_t)P * cm.n, 0.0);
+    if (!p.use_null_firth.empty()) {      // check_firth_file / the list reader (Step2_Models.cpp:1871-1934): `<phenotype> <file>` per line
+      sout << " * reading null Firth estimates using file : [" << p.use_null_firth << "]\n";
+      null_firth_files.assign(P, "");
+      TextIn lf(p.use_null_firth);
+      if (!lf) throw std::runtime_error("cannot read file : " + p.use_null_firth);
+      std::string ln;
+      while (std::getline(lf, ln)) {
+        const auto t = split_ws(ln);
+        if (t.empty()) continue;
+        if (t.size() != 2) throw std::runtime_error("incorrectly formatted file specified by --use-null-firth.");
+        for (int q = 0; q < P; ++q) if (cm.r.pheno_names[q] == t[0]) null_firth_files[q] = t[1];
       }
     }
+    if (p.write_null_firth) sout << " * writing null Firth estimates to file\n";
+    if (cm.firth && !p.firth_approx) blup_off.assign((size_t)P * cm.n, 0.0);
+    if (cm.glm) bt_fit.assign((size_t)P * cm.n, 0.5);
   }
-  static const struct T255 { double v[256]; T255() { for (int b = 0; b < 256; ++b) v[b] = b / 255.0; } } t255;   // the reader's prob = byte / 255.0
-  // the device route of a block: false = not taken (no decoder, or a variant the decoder flagged: the host route then gives the reference's verdict)
-  // reads the stored streams of a group into a slot's page-locked buffer (any thread; the handle is only read)
-  auto read_streams = [&](const BlkRef& br, DosPrep& d, int rows) -> bool {
-    auto t0 = std::chrono::steady_clock::now();
-    const int bs = rows;
-    std::vector<int64_t> vi(bs);
-    for (int j = 0; j < bs; ++j) vi[j] = r.snp_offset[(*br.snps)[br.j0 + j]];
-    int64_t need = 0;
-    if (rg_bgen_compressed_bytes(r.bgenh, bs, vi.data(), &need) != RG_BGEN_OK) return false;
-    if (d.comp_cap < need) {
-      if (d.comp) rg_host_free(d.comp);
-      d.comp_cap = need + need / 4;
-      d.comp = (uint8_t*)rg_host_alloc((size_t)d.comp_cap);
-      if (!d.comp) { d.comp_cap = 0; return false; }
-    }
-    d.rd_off.resize(bs); d.rd_clen.resize(bs); d.rd_ulen.resize(bs);
-    const bool ok = rg_bgen_read_compressed(r.bgenh, bs, vi.data(), d.comp, d.comp_cap, d.rd_off.data(), d.rd_clen.data(), d.rd_ulen.data(), std::min(nt_prep, 32)) == RG_BGEN_OK;
-    d.rd_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ok;
-  };
-  // the first `rows` variants of a group on the device: their sums into d.total ... (sized by the caller), their dosage rows left in device memory
-  auto prepare_dev = [&](const BlkRef& br, DosPrep& d, int slot, int64_t gi, int rows) -> bool {
-    if (!bdev || rows < 1) return false;
-    const int bs = rows;
-    // this group's streams: read ahead (while the previous group was decoded), or now
-    bool have = false;
-    if (d.rd.valid()) { const bool ok = d.rd.get(); have = ok && d.rd_group == gi; }
-    if (!have && !read_streams(br, d, rows)) return false;
-    d.rd_group = -1;
-    // the NEXT group's streams go into the other slot's buffer while this one is decoded (that slot's decode is long done; the main thread
-    // only reads its sums and its device rows)
-    if (gi >= 0 && (size_t)gi + 1 < groups.size() && groups[gi + 1].dev_rows > 0) {
-      DosPrep& dn = preps[(gi + 1) & 1];
-      if (dn.rd.valid()) dn.rd.wait();
-      dn.rd_group = gi + 1;
-      dn.rd = std::async(std::launch::async, [&, gn = gi + 1]() { return read_streams(groups[gn].ref, preps[gn & 1], groups[gn].dev_rows); });
-    }
-    const std::vector<int64_t>& off = d.rd_off;
-    const std::vector<int32_t>&clen = d.rd_clen, &ulen = d.rd_ulen;
-    std::vector<int32_t> status(bs), maxq(bs);
-    auto t1 = std::chrono::steady_clock::now();
-    const bool per_trait = any_missing || glm;
-    std::vector<int64_t> sq(bs), si(bs), no(bs), sqt, sit, nt;
-    if (per_trait) { sqt.resize((size_t)bs * P); sit.resize((size_t)bs * P); nt.resize((size_t)bs * P); }
-    rg_bgen_dev_out o;
-    memset(&o, 0, sizeof(o));
-    o.sum_q = sq.data(); o.sum_info = si.data(); o.n_obs = no.data(); o.max_q = maxq.data(); o.status = status.data();
-    if (per_trait) { o.sum_q_t = sqt.data(); o.sum_info_t = sit.data(); o.n_obs_t = nt.data(); }
-    if (rg_bgen_dev_decode(bdev, slot, bs, d.comp, off[bs - 1] + clen[bs - 1], off.data(), clen.data(), ulen.data(), p.ref_first ? 1 : 0, &o) != RG_BGEN_OK) return false;
-    for (int j = 0; j < bs; ++j) if (status[j] != 0) return false;
-    bool bad = false;
-    for (int j = 0; j < bs; ++j) {
-      // the walk's exact integer sums in the units the host route accumulates as doubles: dosages in 1 / 255, info terms in 1 / 65025
-      d.total[j] = (double)sq[j] / 255.0; d.info_num[j] = (double)si[j] / 65025.0; d.ns1[j] = no[j];
-      if (maxq[j] > 510) bad = true;
-      const double mac = std::min(d.total[j], 2.0 * d.ns1[j] - d.total[j]);
-      // The sum here is the exact integer sum / 255; the host route and regenie add the samples' doubles in order.  A count that lands on
-      // --minMAC to within that summation's rounding could fall on the other side of the `<` there: such a group goes to the host route as a
-      // whole (its verdict is the reference's), so that the filter does not depend on which route a variant took.  (si == 0: every call is a
-      // hard call, the doubles are integers and their sum is exact whatever the order -- the common case of a count that EQUALS --minMAC.)
-      if (si[j] != 0 && std::fabs(mac - p.min_mac) <= 1e-9 * std::max(1.0, mac)) return false;
-      if (mac < p.min_mac) d.ignored[j] = 1;      // compute_mac (Geno.cpp:3077-3108), autosomes
-      if (per_trait)
-        for (int q = 0; q < P; ++q) {      // the host route SUBTRACTS what the samples missing for trait q contribute
-          d.af_t[(size_t)j * P + q] = -(double)sqt[(size_t)j * P + q] / 255.0;
-          d.ns_t[(size_t)j * P + q] = -nt[(size_t)j * P + q];
-          d.info_t[(size_t)j * P + q] = -(double)sit[(size_t)j * P + q] / 65025.0;
-        }
-    }
-    d.dev_bad = bad;
-    d.g16_dev = o.g16; d.ld_dev = o.ld16;
-    auto t2 = std::chrono::steady_clock::now();
-    d.ms_read = have ? 0.0 : d.rd_ms;      // what the read cost THIS group's preparation (read ahead: nothing)
-    d.ms_dev = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return true;
-  };
-  auto prepare = [&](const BlkRef& br, DosPrep& d, int slot, int64_t gi) {
-    try {
-      const int bs = br.bs;
-      auto ta = std::chrono::steady_clock::now();
-      std::vector<int64_t> vi(bs);
-      for (int j = 0; j < bs; ++j) vi[j] = r.snp_offset[(*br.snps)[br.j0 + j]];
-      const bool per_trait = any_missing || glm;
-      d.g16_dev = nullptr; d.ms_read = d.ms_dev = 0; d.dev_rows = 0; d.host_row0 = 0; d.dev_bad = false;
-      d.total.assign(bs, 0.0); d.info_num.assign(bs, 0.0); d.ns1.assign(bs, 0); d.ignored.assign(bs, 0);
-      if (per_trait) { d.af_t.assign((size_t)bs * P, 0.0); d.ns_t.assign((size_t)bs * P, 0); d.info_t.assign((size_t)bs * P, 0.0); }
-      std::atomic<int> bad(0);
-      std::vector<std::string> werr(nt_prep);
-      std::vector<double> w_inf(nt_prep, 0.0), w_walk(nt_prep, 0.0);
-      const bool rf = p.ref_first;
-      // rows [lo, bs) of the group on the host threads, into the pinned buffer from its first row on
-      auto host_rows = [&](int lo) {
-        if (lo >= bs) return;
-        if (d.g16_rows < bs - lo) {
-          if (d.g16) rg_host_free(d.g16);
-          d.g16 = (uint16_t*)rg_host_alloc((size_t)(bs - lo) * ld16 * sizeof(uint16_t));
-          d.g16_rows = d.g16 ? bs - lo : 0;
-          if (!d.g16) throw std::runtime_error("cannot allocate the pinned dosage buffers");
-        }
-        d.host_row0 = lo;
-        d.raw.resize((size_t)nt_prep * bgen_block_bytes);        // one inflated block per worker: walked while it is still in that core's cache
-        std::atomic<int> next(lo);
-        // (no reader lock: the read call only reads the handle, so the parts of a --gpus N run inflate at the same time)
-        parallel_for(nt_prep, nt_prep, [&](int w) {
-          uint8_t* blk = d.raw.data() + (size_t)w * bgen_block_bytes;
-          for (int j; (j = next.fetch_add(1)) < bs;) {
-            auto t0 = std::chrono::steady_clock::now();
-            if (rg_bgen_read_blocks(r.bgenh, 1, &vi[j], blk, bgen_block_bytes, 1) != RG_BGEN_OK) { werr[w] = rg_bgen_last_error(r.bgenh); next = bs; return; }
-            auto t1 = std::chrono::steady_clock::now();
-            const uint8_t* ploidy = blk + 8;
-            const uint8_t* pr = blk + 10 + r.n_file;
-            uint16_t* q16 = d.g16 + (size_t)(j - lo) * ld16;
-            double tot = 0.0, inf = 0.0; int64_t ns = 0;
-            unsigned worst = 0;
-            if (per_trait)
-              for (int q = 0; q < P; ++q) { d.af_t[(size_t)j * P + q] = 0.0; d.ns_t[(size_t)j * P + q] = 0; d.info_t[(size_t)j * P + q] = 0.0; }
-            for (int64_t k = 0; k < n; ++k) {
-              const int64_t i = identity ? k : file_idx[k];
-              if (ploidy[i] & 0x80) { q16[k] = 0xFFFFu; continue; }
-              const unsigned b0 = pr[2 * i], b1 = pr[2 * i + 1];
-              const double p0 = t255.v[b0], p1 = t255.v[b1];
-              double v, e;
-              unsigned qi;
-              if (rf) {     // G = prob1 + 2 prob2, prob2 = max(1 - prob0 - prob1, 0) (Geno.cpp:2286-2290)
-                const double p2 = std::max(1.0 - p0 - p1, 0.0);
-                v = p1 + 2.0 * p2; e = (4.0 * p2 + p1) - v * v;
-                qi = b1 + 2u * (b0 + b1 < 255u ? 255u - b0 - b1 : 0u);
-              } else {
-                v = p1 + 2.0 * p0; e = (4.0 * p0 + p1) - v * v;
-                qi = b1 + 2u * b0;
-              }
-              worst = std::max(worst, qi);
-              q16[k] = (uint16_t)qi;
-              tot += v; inf += e; ++ns;
-              if (per_trait && has_missing[k])
-                for (int q = 0; q < P; ++q)
-                  if (!Mc[(size_t)q * n + k]) { d.af_t[(size_t)j * P + q] -= v; d.ns_t[(size_t)j * P + q] -= 1; d.info_t[(size_t)j * P + q] -= e; }
-            }
-            for (int64_t k = n; k < ld16; ++k) q16[k] = 0;
-            if (worst > 510u) bad = 1;          // prob0 + prob1 > 1 in the file: not a dosage in [0, 2], the general route reports what the reference would
-            d.total[j] = tot; d.ns1[j] = ns; d.info_num[j] = inf;
-            d.ignored[j] = std::min(tot, 2.0 * ns - tot) < p.min_mac ? 1 : 0;      // compute_mac (Geno.cpp:3077-3108), autosomes
-            auto t2 = std::chrono::steady_clock::now();
-            w_inf[w] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-            w_walk[w] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-          }
-        });
-        for (const auto& e : werr) if (!e.empty()) throw std::runtime_error(e);
-      };
-      // the group's first rows on the device and, beside them, its last blocks on the host threads; a group the decoder turns down goes to
-      // the host threads as a whole (a damaged stream, another encoding: their messages are the reference's)
-      const int split = (bdev && gi >= 0) ? groups[gi].dev_rows : 0;
-      bool dev_ok = false;
-      if (split > 0) {
-        std::future<bool> fdev = std::async(std::launch::async, [&]() { return prepare_dev(br, d, slot, gi, split); });
-        try { host_rows(split); } catch (...) { fdev.wait(); throw; }
-        dev_ok = fdev.get();
-      }
-      if (dev_ok) d.dev_rows = split;
-      else { d.g16_dev = nullptr; d.dev_bad = false; host_rows(0); }
-      d.integral = !bad && !d.dev_bad;
-      // thread-milliseconds of the two halves, and the wall time of the block's preparation
-      d.ms_inflate = 0; d.ms_walk = 0;
-      for (int w = 0; w < nt_prep; ++w) { d.ms_inflate += w_inf[w]; d.ms_walk += w_walk[w]; }
-      d.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
-    } catch (const std::exception& e) { d.err = e.what(); if (d.err.empty()) d.err = "bgen read failed"; }
-  };
-  std::future<void> prep_ahead;      // declared after everything `prepare` touches: its destructor waits for the worker before those go away
-  // The read-ahead futures of the device route live in `preps` (declared BEFORE `groups`, which their worker dereferences) and the pinned
-  // buffers / the device decoder are freed by hand at the end of the normal path: on an exception (a failed check, a rethrown reader error)
-  // this guard -- declared after all of them, so destroyed first -- joins the workers and releases what they use, in that order.
-  struct S2Cleanup {
-    std::function<void()> f;
-    bool done = false;
-    rg_bgen_dev** dev = nullptr;
-    void run() { if (!done) { done = true; f(); } }
-    ~S2Cleanup() { run(); if (dev && *dev) { rg_bgen_dev_destroy(*dev); *dev = nullptr; } }
-  } cleanup{[&]() {
-    if (prep_ahead.valid()) prep_ahead.wait();
-    for (auto& d : preps) if (d.rd.valid()) d.rd.wait();
-    for (auto& d : preps) { if (d.g16) rg_host_free(d.g16); if (d.comp) rg_host_free(d.comp); d.g16 = nullptr; d.comp = nullptr; }
-  }};
-  cleanup.dev = &bdev;
-  if (fast_bgen && !groups.empty())      // the first group is inflated while the first chromosome's predictions are read
-    prep_ahead = std::async(std::launch::async, [&]() { prepare(groups[0].ref, preps[0], 0, 0); });
-  for (int chrom : r.chr_read) {
-    if (!chr_snps.count(chrom)) continue;
-    const std::vector<int64_t>& snps = chr_snps[chrom];
-    const int nb_chr = (int)((snps.size() + p.bsize - 1) / p.bsize);
-    if (block + nb_chr <= part.blk_lo || block >= part.blk_hi) { block += nb_chr; continue; }     // none of the chromosome's blocks is this part's
-    sout << "Chromosome " << chrom << " [" << nb_chr << " blocks in total]\n";
-    // blup_read_chr (Step2_Models.cpp:51-140) + compute_res (Data.cpp:2386-2400)
-    sout << (p.bt ? "   -reading loco predictions for the chromosome and fitting null logistic regression on binary phenotypes..."
-                  : p.ct ? "   -reading loco predictions for the chromosome and fitting null poisson regression..." : "   -reading loco predictions for the chromosome...");
-    auto tb = std::chrono::steady_clock::now();
-    // the chromosome's row of every phenotype's .loco file (500,000 numbers each at UK Biobank size): read and converted by one host thread
-    // per phenotype, the checks reported in phenotype order
+
+  // the chromosome's row of every phenotype's .loco file (500,000 numbers each at UK Biobank size): read and converted by one host thread
+  // per phenotype, the checks reported in phenotype order
+  std::vector<std::vector<double>> read_loco(int chrom) const {
+    const Run& r = cm.r;
+    const int P = cm.P;
     std::vector<std::vector<double>> blup_q(P);
     std::vector<std::string> blup_err(P);
-    parallel_for(P, nthreads, [&](int q) {
-      Run::Blup& bl = r.blups[q];
+    parallel_for(P, cm.nthreads, [&](int q) {
+      const Run::Blup& bl = r.blups[q];
       if (chrom < 1 || chrom > (int)bl.line_off.size()) { blup_err[q] = "blup file for phenotype '" + r.pheno_names[q] + "' has no line for chromosome " + std::to_string(chrom) + "."; return; }
       std::string line;
       if (!bl.lines.empty()) line = bl.lines[chrom - 1];
@@ -480,15 +150,15 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
         blup_err[q] = "blup file for phenotype '" + r.pheno_names[q] + "' has different number of entries on line " + std::to_string(chrom + 1) + " compared to the header (=" + std::to_string(nt) + " vs " + std::to_string(bl.col_sample.size()) + ").";
         return;
       }
-      if (chr_str_to_int(std::string(t[0].b, t[0].e), p.nchrom) != chrom) {
+      if (chr_str_to_int(std::string(t[0].b, t[0].e), cm.p.nchrom) != chrom) {
         blup_err[q] = "blup file for phenotype '" + r.pheno_names[q] + "' starts with `" + std::string(t[0].b, t[0].e) + "`instead of chromosome number=" + std::to_string(chrom) + ".";
         return;
       }
       std::vector<double>& blup = blup_q[q];
-      blup.assign(N, 0.0);
+      blup.assign(cm.N, 0.0);
       for (int c = 1; c < nt; ++c) {
         const int64_t i = bl.col_sample[c];
-        if (i < 0 || !r.ain[i] || !r.mask[(size_t)q * N + i]) continue;
+        if (i < 0 || !r.ain[i] || !r.mask[(size_t)q * cm.N + i]) continue;
         const double v = convert_double_tok(t[c].b, t[c].e);
         if (v == MISSING) { blup_err[q] = "individual has missing predictions (chr=" + std::to_string(chrom) + ";phenotype=" + r.pheno_names[q] + ")."; return; }
         blup[i] = v;
@@ -496,481 +166,544 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
     });
     for (int q = 0; q < P; ++q)
       if (!blup_err[q].empty()) throw std::runtime_error(blup_err[q]);
-    const auto tb1 = std::chrono::steady_clock::now();
-    for (int q = 0; q < P; ++q) {
-      const std::vector<double>& blup = blup_q[q];
-      if (glm) {   // fit_null_logistic / fit_null_poisson, test-mode branch (Step1_Models.cpp:54-140, :225-288): offset = the LOCO prediction of
-                   // the analysed, unmasked samples
-        std::vector<double> off(n), eta, pv;
-        for (int64_t k = 0; k < n; ++k) off[k] = blup[an[k]] * Mc[(size_t)q * n + k];
-        const double* yq = Yc.data() + (size_t)q * n;
-        const uint8_t* mq = Mc.data() + (size_t)q * n;
-        bool ok;
-        std::vector<double> bnull;
-        if (p.ct) ok = fit_poisson(yq, Xc.data(), mq, n, C, p, eta, off.data(), &pv);
-        else {
-          LogisticState lst;
-          ok = fit_logistic(yq, Xc.data(), mq, n, C, p, true, eta, off.data(), &pv, &bnull, &lst);
-          if (!ok) ok = fit_logistic(yq, Xc.data(), mq, n, C, p, false, eta, off.data(), &pv, &bnull, &lst);
+    return blup_q;
+  }
+
+  // fit_null_logistic / fit_null_poisson, test-mode branch (Step1_Models.cpp:54-140, :225-288): offset = the LOCO prediction of the
+  // analysed, unmasked samples
+  void fit_glm(int chrom, int q, const std::vector<double>& blup) {
+    const Params& p = cm.p;
+    const int C = cm.C;
+    const int64_t n = cm.n;
+    const std::vector<int64_t>& an = cm.an;
+    const std::vector<double>& Xc = cm.Xc;
+    std::vector<double> off(n), eta, pv;
+    for (int64_t k = 0; k < n; ++k) off[k] = blup[an[k]] * cm.Mc[(size_t)q * n + k];
+    const double* yq = cm.Yc.data() + (size_t)q * n;
+    const uint8_t* mq = cm.Mc.data() + (size_t)q * n;
+    bool ok;
+    std::vector<double> bnull;
+    if (p.ct) ok = fit_poisson(yq, Xc.data(), mq, n, C, p, eta, off.data(), &pv);
+    else {
+      LogisticState lst;
+      ok = fit_logistic(yq, Xc.data(), mq, n, C, p, true, eta, off.data(), &pv, &bnull, &lst);
+      if (!ok) ok = fit_logistic(yq, Xc.data(), mq, n, C, p, false, eta, off.data(), &pv, &bnull, &lst);
+    }
+    if (ok && cm.firth) {   // fit_null_firth (Step2_Models.cpp:985-1060): penalised fit of the covariates, start = the unpenalised estimate
+      if (!null_firth_files.empty() && !null_firth_files[q].empty()) {   // --use-null-firth: the stored estimates of this chromosome as start
+        TextIn nf(null_firth_files[q]);                                   // (get_beta_start_firth, Step2_Models.cpp:1936-1981)
+        if (!nf) throw std::runtime_error("cannot read file : " + null_firth_files[q]);
+        std::string ln;
+        while (std::getline(nf, ln)) {
+          const auto t = split_ws(ln);
+          if (t.empty()) throw std::runtime_error("error reading null firth estimates file");
+          if (chr_str_to_int(t[0], p.nchrom) != chrom) continue;
+          if ((int)t.size() - 1 > C) throw std::runtime_error("file has more predictors than included in analysis (=" + std::to_string(t.size()) + " vs " + std::to_string(C) + ")");
+          for (size_t c = 1; c < t.size(); ++c) {
+            const double v = convert_double(t[c]);
+            if (v == MISSING) throw std::runtime_error("no missing values allowed in file");
+            bnull[c - 1] = v;
+          }
+          break;
         }
-        if (ok && firth) {   // fit_null_firth (Step2_Models.cpp:985-1060): penalised fit of the covariates, start = the unpenalised estimate
-          if (!null_firth_files.empty() && !null_firth_files[q].empty()) {   // --use-null-firth: the stored estimates of this chromosome as start
-            TextIn nf(null_firth_files[q]);                                   // (get_beta_start_firth, Step2_Models.cpp:1936-1981)
-            if (!nf) throw std::runtime_error("cannot read file : " + null_firth_files[q]);
-            std::string ln;
-            while (std::getline(nf, ln)) {
-              const auto t = split_ws(ln);
-              if (t.empty()) throw std::runtime_error("error reading null firth estimates file");
-              if (chr_str_to_int(t[0], p.nchrom) != chrom) continue;
-              if ((int)t.size() - 1 > C) throw std::runtime_error("file has more predictors than included in analysis (=" + std::to_string(t.size()) + " vs " + std::to_string(C) + ")");
-              for (size_t c = 1; c < t.size(); ++c) {
-                const double v = convert_double(t[c]);
-                if (v == MISSING) throw std::runtime_error("no missing values allowed in file");
-                bnull[c - 1] = v;
-              }
-              break;
-            }
-          }
-          ok = firth_null_fit(yq, Xc.data(), mq, off.data(), n, C, bnull);
-          if (ok && p.write_null_firth) {     // (*firth_est_files[i]) << chrom << " " << bvec (Step2_Models.cpp:1019-1020)
-            std::ostringstream ln;
-            ln << chrom << " ";
-            for (int c = 0; c < C; ++c) ln << bnull[c] << (c + 1 < C ? " " : "");
-            firth_file_body[q] += ln.str() + "\n";
-          }
-          if (!ok) sout << "\n     WARNING: null Firth failed for phenotype '" << r.pheno_names[q] << "' (it will be skipped).";
-          for (int64_t k = 0; ok && k < n; ++k) {
-            double e = blup[an[k]];
-            for (int c = 0; c < C; ++c) e += Xc[(size_t)c * n + k] * bnull[c];
-            firth_off[(size_t)q * n + k] = e;
-            if (!p.firth_approx) blup_off[(size_t)q * n + k] = blup[an[k]];
-          }
-          for (int c = 0; ok && c < C; ++c) firth_bnull[(size_t)q * C + c] = bnull[c];
-        }
-        bt_pass[q] = ok ? 1 : 0;
-        if (!ok) { if (!(firth && !bnull.empty())) sout << "\n     WARNING: " << (p.ct ? "poisson" : "logistic") << " regression did not converge for phenotype '" << r.pheno_names[q] << "'."; continue; }
-        // the fitted mean of the null model: the library forms Gamma_sqrt^2, the weighted covariates and (X^T W X)^-1 from it (rg_s2_bt_set_null)
-        for (int64_t k = 0; k < n; ++k) bt_fit[(size_t)q * n + k] = pv[k];
-        continue;
       }
+      ok = firth_null_fit(yq, Xc.data(), mq, off.data(), n, C, bnull);
+      if (ok && p.write_null_firth) {     // (*firth_est_files[i]) << chrom << " " << bvec (Step2_Models.cpp:1019-1020)
+        std::ostringstream ln;
+        ln << chrom << " ";
+        for (int c = 0; c < C; ++c) ln << bnull[c] << (c + 1 < C ? " " : "");
+        firth_file_body[q] += ln.str() + "\n";
+      }
+      if (!ok) sout << "\n     WARNING: null Firth failed for phenotype '" << cm.r.pheno_names[q] << "' (it will be skipped).";
+      for (int64_t k = 0; ok && k < n; ++k) {
+        double e = blup[an[k]];
+        for (int c = 0; c < C; ++c) e += Xc[(size_t)c * n + k] * bnull[c];
+        firth_off[(size_t)q * n + k] = e;
+        if (!p.firth_approx) blup_off[(size_t)q * n + k] = blup[an[k]];
+      }
+      for (int c = 0; ok && c < C; ++c) firth_bnull[(size_t)q * C + c] = bnull[c];
+    }
+    bt_pass[q] = ok ? 1 : 0;
+    if (!ok) { if (!(cm.firth && !bnull.empty())) sout << "\n     WARNING: " << (p.ct ? "poisson" : "logistic") << " regression did not converge for phenotype '" << cm.r.pheno_names[q] << "'."; return; }
+    // the fitted mean of the null model: the library forms Gamma_sqrt^2, the weighted covariates and (X^T W X)^-1 from it (rg_s2_bt_set_null)
+    for (int64_t k = 0; k < n; ++k) bt_fit[(size_t)q * n + k] = pv[k];
+  }
+
+  // blup_read_chr (Step2_Models.cpp:51-140) + compute_res (Data.cpp:2386-2400)
+  void set_up(int chrom, rg_s2_ctx* s2) {
+    const Params& p = cm.p;
+    const int64_t n = cm.n;
+    sout << (p.bt ? "   -reading loco predictions for the chromosome and fitting null logistic regression on binary phenotypes..."
+                  : p.ct ? "   -reading loco predictions for the chromosome and fitting null poisson regression..." : "   -reading loco predictions for the chromosome...");
+    auto tb = std::chrono::steady_clock::now();
+    const std::vector<std::vector<double>> blup_q = read_loco(chrom);
+    const auto tb1 = std::chrono::steady_clock::now();
+    for (int q = 0; q < cm.P; ++q) {
+      const std::vector<double>& blup = blup_q[q];
+      if (cm.glm) { fit_glm(chrom, q, blup); continue; }
       double ss = 0.0;
       for (int64_t k = 0; k < n; ++k) {
-        const double v = (Yc[(size_t)q * n + k] - blup[an[k]]) * Mc[(size_t)q * n + k];
+        const double v = (cm.Yc[(size_t)q * n + k] - blup[cm.an[k]]) * cm.Mc[(size_t)q * n + k];
         resc[(size_t)q * n + k] = v;
         ss += v * v;
       }
-      const double sd = std::sqrt(ss) / std::sqrt(r.neff[q] - C);
+      const double sd = std::sqrt(ss) / std::sqrt(cm.r.neff[q] - cm.C);
       for (int64_t k = 0; k < n; ++k) resc[(size_t)q * n + k] /= sd;
-      scf[q] = r.scale_Y[q] * sd;
+      scf[q] = cm.r.scale_Y[q] * sd;
     }
     const auto tb2 = std::chrono::steady_clock::now();
-    if (glm) {   // compute_res_bin / compute_res_count (Data.cpp:2439-2455): the null models of the chromosome go to the device
+    int rc;
+    if (cm.glm) {   // compute_res_bin / compute_res_count (Data.cpp:2439-2455): the null models of the chromosome go to the device
       rg_s2_bt_null nm;
       memset(&nm, 0, sizeof(nm));
-      nm.family = p.ct ? 1 : 0; nm.niter_max = p.niter_max; nm.X = Xc.data(); nm.y = Yc.data(); nm.mask = Mc.data(); nm.fitted = bt_fit.data();
-      nm.firth_offset = (firth && p.firth_approx) ? firth_off.data() : nullptr; nm.pass = bt_pass.data();
-      s2check(rg_s2_bt_set_null(s2, &nm));
-    } else s2check(rg_s2_set_null(s2, Xc.data(), resc.data(), Mc.data(), scf.data()));
+      nm.family = p.ct ? 1 : 0; nm.niter_max = p.niter_max; nm.X = cm.Xc.data(); nm.y = cm.Yc.data(); nm.mask = cm.Mc.data(); nm.fitted = bt_fit.data();
+      nm.firth_offset = (cm.firth && p.firth_approx) ? firth_off.data() : nullptr; nm.pass = bt_pass.data();
+      rc = rg_s2_bt_set_null(s2, &nm);
+    } else rc = rg_s2_set_null(s2, cm.Xc.data(), resc.data(), cm.Mc.data(), scf.data());
+    if (rc != RG_S2_OK) throw std::runtime_error(rg_s2_last_error(s2));
     sout << "done (" << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - tb).count() << "ms) \n";
-    ms_chr += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
-    if (getenv("RG_TIMING"))
+    ms_chr += ms_since(tb);
+    if (cm.env.timing)
       fprintf(stderr, "[timing] chromosome %d set-up: predictions read + converted %.0f ms, null models / residuals %.0f ms, to the device %.0f ms\n", chrom,
-              std::chrono::duration<double, std::milli>(tb1 - tb).count(), std::chrono::duration<double, std::milli>(tb2 - tb1).count(),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb2).count());
+              std::chrono::duration<double, std::milli>(tb1 - tb).count(), std::chrono::duration<double, std::milli>(tb2 - tb1).count(), ms_since(tb2));
+  }
+};
 
+// what every input route of a block fills: allele totals, observed samples, the info-score numerator, and per trait [bs][P] their
+// DIFFERENCES from those for the samples the trait masks (only filled with S2Common::per_trait)
+struct BlockCounts {
+  std::vector<double> total, info_num, af_t, info_t;
+  std::vector<int64_t> ns1, ns_t;
+  std::vector<uint8_t> variant_ignored;
+  explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0) {}
+};
+
+// One block through the tests: an input route leaves the counts and the genotype source, the scorer the statistics, correct() the
+// Firth / saddlepoint results, format() the result lines.  The buffers are kept from block to block.
+struct S2Block {
+  const S2Common& cm;
+  const ChromNull& null;
+  rg_s2_ctx* s2;
+  S2Block(const S2Common& cm_, const ChromNull& null_, rg_s2_ctx* s2_) : cm(cm_), null(null_), s2(s2_) {}
+  void check(int rc) const { if (rc != RG_S2_OK) throw std::runtime_error(rg_s2_last_error(s2)); }
+
+  int bs = 0;
+  std::vector<int64_t> vidx;                        // the block's variants in the file
+  std::vector<uint8_t> rows_buf, packed;
+  std::vector<double> dbuf, ibuf, G;
+  std::vector<uint16_t> G16;
+  // the source an input route leaves for the scorer: 2-bit rows (hard calls), uint16 rows (integral) or the doubles of G
+  const uint8_t* rows = nullptr; int64_t ld = 0;
+  bool integral = false;
+  const uint16_t* g16p = nullptr; int64_t g16ld = 0; int g16_on_device = 0;
+  // statistics and corrections per (variant, trait)
+  std::vector<double> stats, bhat, sfac, denum_v, mu_v, corr_beta, corr_se, corr_chisq, corr_logp;
+  std::vector<int32_t> ign;
+  std::vector<uint8_t> test_ignored, sparse_v, corrected, corr_fail;
+
+  void begin(int bs_) {
+    bs = bs_;
+    stats.resize((size_t)bs * cm.P); bhat.resize((size_t)bs * cm.P); sfac.resize(bs); ign.resize(bs);
+    test_ignored.assign((size_t)bs * cm.P, 0);
+    integral = false; g16p = nullptr; g16ld = cm.n; g16_on_device = 0;
+  }
+
+  // reads of the routes that go through a reader handle (the caller holds the reader's lock in a multi-GPU run)
+  void read_pgen_hard() {   // ReadHardcalls per variant (Geno.cpp:2570-2573), as .bed-coded rows (00 = two ALT copies)
+    rows_buf.resize((size_t)bs * cm.r.bpr);
+    if (rg_pgen_read_bed_rows(cm.r.pgen, bs, vidx.data(), rows_buf.data(), cm.r.bpr) != RG_PGEN_OK) throw std::runtime_error(rg_pgen_last_error(cm.r.pgen));
+    rows = rows_buf.data();
+  }
+  void read_dosage_rows() {
+    const Run& r = cm.r;
+    dbuf.resize((size_t)bs * r.n_file);
+    if (r.bgenh) {            // parseSnpfromBGEN (Geno.cpp:2186-2330): dosages and the terms of the IMPUTE info score
+      ibuf.resize((size_t)bs * r.n_file);
+      if (rg_bgen_read_dosages_info(r.bgenh, bs, vidx.data(), cm.p.ref_first ? 1 : 0, dbuf.data(), ibuf.data(), r.n_file) != RG_BGEN_OK)
+        throw std::runtime_error(rg_bgen_last_error(r.bgenh));
+    } else if (rg_pgen_read_dosage_rows(r.pgen, bs, vidx.data(), dbuf.data(), r.n_file) != RG_PGEN_OK)   // Read() (Geno.cpp:2570-2571)
+      throw std::runtime_error(rg_pgen_last_error(r.pgen));
+  }
+
+  // route 1: the block the BGEN read-ahead prepared
+  void from_prepared(const PreparedBlock& pb, BlockCounts& bc) {
+    const size_t P = (size_t)cm.P;
+    bc.total.assign(pb.total, pb.total + bs); bc.ns1.assign(pb.ns1, pb.ns1 + bs);
+    bc.info_num.assign(pb.info_num, pb.info_num + bs);
+    bc.variant_ignored.assign(pb.ignored, pb.ignored + bs);
+    if (cm.per_trait) { bc.af_t.assign(pb.af_t, pb.af_t + bs * P); bc.ns_t.assign(pb.ns_t, pb.ns_t + bs * P); bc.info_t.assign(pb.info_t, pb.info_t + bs * P); }
+    integral = true; g16p = pb.g16; g16ld = pb.ld; g16_on_device = pb.on_device;
+  }
+
+  // route 2, general dosage rows: the analysed samples' doubles, allele totals, the info-score numerator and the per-trait corrections on the
+  // host (parseSnpfromBGEN / readChunkFromPGENFileToG with update_trait_counts, Geno.cpp:2948-2959)
+  void from_dosage_rows(BlockCounts& bc) {
+    const Run& r = cm.r;
+    const int P = cm.P, dscale = cm.dscale;
+    const int64_t n = cm.n;
+    G.assign((size_t)bs * n, 0.0);
+    bc.info_num.assign(bs, 0.0);
+    if (cm.per_trait) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); bc.info_t.assign((size_t)bs * P, 0.0); }
+    parallel_for(bs, cm.nthreads, [&](int j) {
+      const double* d = dbuf.data() + (size_t)j * r.n_file;
+      const double* iv = r.bgenh ? ibuf.data() + (size_t)j * r.n_file : nullptr;
+      double* g = G.data() + (size_t)j * n;
+      double tot = 0.0, inf = 0.0; int64_t ns = 0;
+      for (int64_t k = 0; k < n; ++k) {
+        const int64_t i = cm.file_idx[k];
+        const double v = d[i];
+        g[k] = v;
+        if (v == -3.0) continue;
+        const double e = iv ? iv[i] : v * v;
+        tot += v; inf += e; ++ns;
+        if (cm.per_trait && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, v, e, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], &bc.info_t[(size_t)j * P]);
+      }
+      bc.total[j] = tot; bc.ns1[j] = ns; bc.info_num[j] = inf;
+      if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
+    });
+    // 8-bit .bgen probabilities and .pgen dosages are integers in units of 1 / 255 and 1 / 16384: as uint16 rows they take the
+    // integer route of the library (digit planes on the i8 matrix cores, 2 B per genotype over PCIe); anything else, or
+    // RG_S2_DENSE=1, the fp64 route
+    integral = !cm.env.dense || cm.glm;
+    if (!integral) return;
+    G16.resize((size_t)bs * n);
+    std::vector<uint8_t> bad(bs, 0);
+    parallel_for(bs, cm.nthreads, [&](int j) {
+      const double* g = G.data() + (size_t)j * n;
+      uint16_t* q = G16.data() + (size_t)j * n;
+      for (int64_t k = 0; k < n; ++k) {
+        if (g[k] == -3.0) { q[k] = 0xFFFFu; continue; }
+        const double v = g[k] * dscale, rv = std::nearbyint(v);
+        if (std::fabs(v - rv) > 1e-6 || rv < 0 || rv > 2.0 * dscale) { bad[j] = 1; break; }
+        q[k] = (uint16_t)rv;
+      }
+    });
+    for (int j = 0; j < bs; ++j) if (bad[j]) integral = false;
+    g16p = G16.data();
+  }
+
+  // route 3, hard calls stay packed: the 2-bit codes of the analysed samples go to the device as they are (the rows of the file itself
+  // when no sample was dropped), the library counts the calls and contracts them on the i8 matrix cores; the counts come with the scores
+  void from_packed() {
+    ld = cm.r.bpr;
+    if (cm.identity) return;
+    ld = repack_analysed(rows, cm.r.bpr, bs, cm.file_idx.data(), cm.n, cm.nthreads, packed);
+    rows = packed.data();
+  }
+
+  // route 4 (RG_S2_DENSE=1), parseSnpfromBed: decode the analysed samples, allele counts
+  void from_dense_bed(BlockCounts& bc) {
+    const int P = cm.P, flip = cm.flip;
+    const int64_t n = cm.n;
+    G.assign((size_t)bs * n, 0.0);
+    if (cm.any_missing) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); }
+    parallel_for(bs, cm.nthreads, [&](int j) {
+      const uint8_t* row = rows + (size_t)j * cm.r.bpr;
+      double* g = G.data() + (size_t)j * n;
+      double tot = 0.0; int64_t ns = 0;
+      for (int64_t k = 0; k < n; ++k) {
+        const int64_t i = cm.file_idx[k];
+        double hc = lut[(row[i >> 2] >> (2 * (i & 3))) & 3];
+        if (flip && hc != -3.0) hc = 2.0 - hc;
+        g[k] = hc;
+        if (hc != -3.0) {
+          tot += hc; ++ns;
+          if (cm.any_missing && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, hc, 0.0, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], nullptr);
+        }
+      }
+      bc.total[j] = tot; bc.ns1[j] = ns;
+      if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
+    });
+  }
+
+  // quantitative traits: the block's statistics from whatever source the route left
+  void score_qt(BlockCounts& bc) {
+    const int P = cm.P;
+    rg_s2_qt_out o;
+    memset(&o, 0, sizeof(o));
+    o.stats = stats.data(); o.bhat = bhat.data(); o.scale_fac = sfac.data(); o.ignored = ign.data();
+    if (cm.in == In::Dosage) {
+      if (integral) check(rg_s2_qt_block_int(s2, g16p, g16ld, bs, g16_on_device, cm.dscale, NUMTOL, &o));
+      else check(rg_s2_qt_block(s2, G.data(), cm.n, bs, 0, NUMTOL, &o));
+      return;
+    }
+    if (cm.env.dense) { check(rg_s2_qt_block(s2, G.data(), cm.n, bs, 0, NUMTOL, &o)); return; }
+    std::vector<double> mean_v(bs), totp_v;
+    std::vector<int32_t> nobs_v(bs), nobsp_v;
+    o.mean = mean_v.data(); o.n_obs = nobs_v.data();
+    if (cm.any_missing) {
+      totp_v.resize((size_t)bs * P); nobsp_v.resize((size_t)bs * P);
+      o.total_p = totp_v.data(); o.n_obs_p = nobsp_v.data();
+    }
+    check(rg_s2_qt_block_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &o));
+    if (cm.any_missing) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); }
+    for (int j = 0; j < bs; ++j) {
+      bc.ns1[j] = nobs_v[j];
+      bc.total[j] = std::nearbyint(mean_v[j] * (double)nobs_v[j]);       // the allele count is an integer: mean = total / n_obs
+      if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
+      if (cm.any_missing)                                                  // update_trait_counts (Geno.cpp:2948-2959) as differences from the totals
+        for (int q = 0; q < P; ++q) {
+          bc.af_t[(size_t)j * P + q] = std::nearbyint(totp_v[(size_t)j * P + q]) - bc.total[j];
+          bc.ns_t[(size_t)j * P + q] = (int64_t)nobsp_v[(size_t)j * P + q] - bc.ns1[j];
+        }
+    }
+  }
+
+  // binary / count traits: the score test of the block through the C ABI (rg_s2_bt_score_*: contractions on the i8 matrix cores, C x C
+  // algebra in the library): hard calls as packed rows, dosages as integer rows
+  void score_glm(BlockCounts& bc) {
+    const int P = cm.P;
+    std::vector<int32_t> bt_counts((size_t)bs * 4), nobsp((size_t)bs * P, 0);
+    std::vector<double> bt_vstat((size_t)bs * 4), totp((size_t)bs * P, 0.0);
+    denum_v.assign((size_t)bs * P, 0.0);
+    mu_v.assign(bs, 0.0); sparse_v.assign(bs, 0);
+    rg_s2_bt_out bo;
+    memset(&bo, 0, sizeof(bo));
+    bo.stats = stats.data(); bo.bhat = bhat.data(); bo.denum = denum_v.data(); bo.test_ignored = test_ignored.data(); bo.mean = mu_v.data();
+    bo.ignored = ign.data(); bo.sparse = sparse_v.data();
+    const bool dosage = cm.in == In::Dosage;
+    if (dosage) {
+      if (!integral) throw std::runtime_error("--step 2 --bt / --ct on dosages that are not integer multiples of 1/" + std::to_string(cm.dscale) + " is not built.");
+      bo.vstat = bt_vstat.data();
+      check(rg_s2_bt_score_int(s2, g16p, g16ld, bs, g16_on_device, cm.dscale, NUMTOL, &bo));
+    } else {
+      bo.counts = bt_counts.data(); bo.total_p = totp.data(); bo.n_obs_p = nobsp.data();
+      check(rg_s2_bt_score_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &bo));
+      bc.af_t.assign(totp.begin(), totp.end());      // per-trait allele and sample counts (dosages: the route has them, summed as the reference sums)
+      bc.ns_t.assign(nobsp.begin(), nobsp.end());
+    }
+    for (int j = 0; j < bs; ++j) {
+      if (!dosage) {
+        const double n1 = bt_counts[(size_t)j * 4], n2 = bt_counts[(size_t)j * 4 + 1], nm = bt_counts[(size_t)j * 4 + 2];
+        bc.ns1[j] = (int64_t)((double)cm.n - nm); bc.total[j] = n1 + 2.0 * n2;
+      }
+      sfac[j] = 1.0;
+      if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
+    }
+  }
+
+  // check_pval_snp (Step2_Models.cpp:1987-2029): |z| above the threshold -> run_SPA_test (--spa) or fit_firth_logistic_snp_fast on Gres / Gamma_sqrt
+  // with the null Firth model's covariate effects in the offset.  The flagged (variant, trait) pairs are re-tested on the device, one
+  // workgroup per pair (rg_s2_bt_correct); the exact Firth test (--firth without --approx: a C + 1 parameter fit) stays on the host threads.
+  void correct(const BlockCounts& bc) {
+    const Params& p = cm.p;
+    const int P = cm.P, C = cm.C;
+    const int64_t n = cm.n;
+    corrected.assign((size_t)bs * P, 0); corr_fail.assign((size_t)bs * P, 0);
+    corr_beta.assign((size_t)bs * P, 0.0); corr_se.assign((size_t)bs * P, 0.0); corr_chisq.assign((size_t)bs * P, 0.0); corr_logp.assign((size_t)bs * P, -1.0);
+    std::vector<int> todo;
+    for (int j = 0; j < bs; ++j)
+      for (int q = 0; q < P; ++q)
+        if (!bc.variant_ignored[j] && !ign[j] && !test_ignored[(size_t)j * P + q] && std::fabs(stats[(size_t)j * P + q]) > cm.z_thr) todo.push_back(j * P + q);
+    if (cm.spa || p.firth_approx) {
+      std::vector<int32_t> pv_(todo.size()), pt_(todo.size());
+      std::vector<uint8_t> pf_(todo.size());
+      for (size_t t = 0; t < todo.size(); ++t) {
+        const int j = todo[t] / P, q = todo[t] % P;
+        pv_[t] = j; pt_[t] = q;
+        if (cm.spa) pf_[t] = sparse_v[j];                                                            // fastSPA (Step2_Models.cpp:2087-2097)
+        else {
+          const double tq = bc.total[j] + bc.af_t[(size_t)j * P + q];
+          const double nsq = (double)(bc.ns1[j] + bc.ns_t[(size_t)j * P + q]);
+          pf_[t] = sparse_v[j] && below_min_mac(tq, nsq, 50.0);                                       // fit_firth_logistic_snp_fast :1173-1185: carriers only
+        }
+      }
+      std::vector<rg_s2_bt_corr> cr(todo.size());
+      check(rg_s2_bt_correct(s2, cm.spa ? RG_S2_BT_SPA : RG_S2_BT_FIRTH_APPROX, (int32_t)todo.size(), pv_.data(), pt_.data(), pf_.data(), p.firth_se ? 1 : 0, cr.data()));
+      for (size_t t = 0; t < todo.size(); ++t) {
+        const size_t e = (size_t)todo[t];
+        corrected[e] = 1;
+        if (cr[t].fail) { corr_fail[e] = 1; continue; }
+        corr_beta[e] = cr[t].beta; corr_se[e] = cr[t].se; corr_chisq[e] = cr[t].chisq; corr_logp[e] = cr[t].logp;
+      }
+      return;
+    }
+    parallel_for((int)todo.size(), cm.nthreads, [&](int t) {
+      const int j = todo[t] / P, q = todo[t] % P;
+      const double mu = mu_v[j];
+      std::vector<double> gt(n);                // the mean-imputed genotype of the analysed samples
+      if (cm.in == In::Dosage) { const double* g = G.data() + (size_t)j * n; for (int64_t k = 0; k < n; ++k) gt[k] = g[k] == -3.0 ? mu : g[k]; }
+      else {
+        const uint8_t* row = rows + (size_t)j * ld;
+        for (int64_t k = 0; k < n; ++k) {
+          double hc = lut[(row[k >> 2] >> (2 * (k & 3))) & 3];
+          if (cm.flip && hc != -3.0) hc = 2.0 - hc;
+          gt[k] = hc == -3.0 ? mu : hc;
+        }
+      }
+      // the exact test (fit_firth_logistic_snp, Step2_Models.cpp:1062-1156): design [covariates | g~ on its raw scale], offset = the LOCO
+      // prediction; null fit = the variant's coefficient held at 0 under the same penalty, then every coefficient free
+      const uint8_t* mq = cm.Mc.data() + (size_t)q * n;
+      const double *yq = cm.Yc.data() + (size_t)q * n, *oq = null.blup_off.data() + (size_t)q * n;
+      std::vector<const double*> cols(C + 1);
+      for (int c = 0; c < C; ++c) cols[c] = cm.Xc.data() + (size_t)c * n;
+      cols[C] = gt.data();
+      std::vector<double> bf(C + 1, 0.0), inv;
+      for (int c = 0; c < C; ++c) bf[c] = null.firth_bnull[(size_t)q * C + c];
+      double dev0 = 0.0, dev1 = 0.0;
+      corrected[(size_t)j * P + q] = 1;
+      const bool okx = firth_fit_cols(yq, cols, mq, oq, n, C, 25.0, bf, &dev0) && firth_fit_cols(yq, cols, mq, oq, n, C + 1, 5.0, bf, &dev1, &inv);
+      const double lrt = dev0 - dev1;
+      if (!okx || lrt < 0) { corr_fail[(size_t)j * P + q] = 1; return; }
+      corr_beta[(size_t)j * P + q] = bf[C];
+      corr_chisq[(size_t)j * P + q] = lrt;
+      corr_se[(size_t)j * P + q] = (p.firth_se && lrt > 0) ? std::fabs(bf[C]) / std::sqrt(lrt) : std::sqrt(inv[(size_t)C * (C + 1) + C]);
+    });
+  }
+
+  // the result lines (compute_score_qt after the statistic, Step2_Models.cpp:440-466; print_sum_stats_single): formatted by the host threads
+  // in contiguous chunks of variants, appended to the files in order; n_ign[3] += ignored variants, ignored tests, tests
+  void format(BlockCounts& bc, const std::vector<int64_t>& snps, int64_t j0, std::vector<std::unique_ptr<TextOut>>& ofs, int64_t* n_ign) {
+    const Run& r = cm.r;
+    const Params& p = cm.p;
+    const int P = cm.P;
+    const bool show_info = cm.show_info, bgen = r.bgenh != nullptr;
+    const int nchunk = std::max(1, std::min(cm.nthreads, bs / 64));
+    std::vector<std::string> chunk_out((size_t)nchunk * P);
+    std::vector<int64_t> c_snps(nchunk, 0), c_tests(nchunk, 0), c_tested(nchunk, 0);
+    parallel_for(nchunk, nchunk, [&](int t) {
+      for (int j = (int)((int64_t)bs * t / nchunk), je = (int)((int64_t)bs * (t + 1) / nchunk); j < je; ++j) {
+        const double total = bc.total[j];
+        const int64_t ns1 = bc.ns1[j];
+        if (!bc.variant_ignored[j] && show_info && p.set_min_info && ns1 > 0)    // the all-sample info score below --minINFO drops the variant (Geno.cpp:2349-2353)
+          if (info_score(bgen, bc.info_num[j], (double)ns1, total / (2.0 * ns1)) < p.min_info) bc.variant_ignored[j] = 1;
+        if (bc.variant_ignored[j] || ign[j]) { ++c_snps[t]; continue; }
+        const int64_t sj = snps[j0 + j];
+        std::ostringstream head;
+        head << r.snp_chrom[sj] << " " << r.snp_pos[sj] << " " << r.snp_ids[sj] << " " << r.snp_a0[sj] << " " << r.snp_a1[sj] << " ";
+        for (int q = 0; q < P; ++q) {
+          const size_t e = (size_t)j * P + q;
+          double af = total / (2.0 * ns1);
+          int64_t nsq = ns1;
+          double infq = show_info ? bc.info_num[j] : 0.0;
+          if (test_ignored[e]) continue;
+          if (cm.per_trait) {   // compute_mac / compute_aaf_info per trait
+            const double tq = total + bc.af_t[e];
+            nsq = ns1 + bc.ns_t[e];
+            if (below_min_mac(tq, (double)nsq, p.min_mac)) { ++c_tests[t]; continue; }
+            af = tq / (2.0 * nsq);
+            if (show_info) infq += bc.info_t[e];
+          }
+          const double info = show_info ? info_score(bgen, infq, (double)nsq, af) : 1.0;
+          if (show_info && p.set_min_info && info < p.min_info) { ++c_tests[t]; continue; }     // ignored_trait (Geno.cpp:3143-3144)
+          const double st = stats[e];
+          double bh = bhat[e], se = bh / st, chisq = st * st;
+          bool test_fail = false;
+          double logp_spa = -1.0;
+          if (cm.correct && corrected[e]) {
+            if (corr_fail[e]) test_fail = true;                    // get_sumstats(true, ...): the score test's BETA / SE, no p-value
+            else { bh = corr_beta[e]; se = corr_se[e]; chisq = corr_chisq[e]; logp_spa = corr_logp[e]; }
+          }
+          const double logp = logp_spa >= 0 ? logp_spa : get_logp(chisq);       // --spa prints the p-value it computed, the chi-square is derived from it
+          std::ostringstream ln;
+          if (af >= 0) ln << head.str() << af << " ";            // print_sum_stats_single (Step2_Models.cpp:2505-2518): a negative value is "NA"
+          else ln << head.str() << "NA ";
+          if (show_info) { if (info >= 0) ln << info << " "; else ln << "NA "; }      // (the IMPUTE score of very uncertain dosages can be negative)
+          ln << nsq << " ADD ";
+          if (se >= 0 && !std::isnan(se)) ln << bh << ' ' << se;
+          else ln << "NA NA";
+          if (chisq >= 0 && !std::isnan(logp) && !test_fail) ln << ' ' << chisq << ' ' << logp;
+          else ln << " NA NA";
+          ln << (test_fail ? " TEST_FAIL\n" : " NA\n");
+          chunk_out[(size_t)t * P + q] += ln.str();
+          ++c_tested[t];
+        }
+      }
+    });
+    for (int t = 0; t < nchunk; ++t) {
+      for (int q = 0; q < P; ++q) *ofs[q] << chunk_out[(size_t)t * P + q];
+      n_ign[0] += c_snps[t]; n_ign[1] += c_tests[t]; n_ign[2] += c_tested[t];
+    }
+  }
+};
+
+int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& part) {
+  const S2Common cm(r, part);
+  const Params& p = cm.p;
+  const int P = cm.P;
+  ChromNull null(cm);
+  rg_s2_ctx* s2 = nullptr;
+  if (rg_s2_create(&s2, part.device, cm.n, cm.C, P) != RG_S2_OK || !s2) throw std::runtime_error("no MI355X / HIP device available (rg_s2_create failed)");
+  S2Block blk(cm, null, s2);
+  // check_sparse_G: params.n_samples, params.prop_zero_thr (Regenie.hpp:311); the .pgen reader counts the observed zeros itself
+  blk.check(rg_s2_set_sparse_rule(s2, cm.N, 0.5, r.pgen ? 1 : 0));
+  // in_non_par (Geno.cpp:2419, :2251): outside the pseudo-autosomal regions of chromosome X the reference halves the males' calls in the
+  // MAC (and, with the default dosage compensation off, nothing else) -- with no male in the sample file that is the autosomal rule
+  if (cm.chr_snps.count(p.nchrom) && r.has_male)
+    throw std::runtime_error("--step 2 on chromosome " + std::to_string(p.nchrom) + " (X) with male samples: the sex-aware allele counts of the non-PAR region "
+                             "are not built; test the autosomes (or supply a sample file without sex codes of 1).");
+  sout << std::left << std::setw(20) << " * block size" << ": [" << p.bsize << "]\n";
+  sout << std::left << std::setw(20) << " * # blocks" << ": [" << cm.total_blocks << "]\n";
+  sout << " * approximate memory usage : n/a (genotype blocks are tested on the GPU)\n";
+  sout << " * using minimum MAC of " << p.min_mac << " (variants with lower MAC are ignored)\n";
+
+  // output files, one per phenotype (split_by_pheno is the default; print_header_output_single, Step2_Models.cpp:2386-2398)
+  std::vector<std::unique_ptr<TextOut>> ofs;
+  for (int q = 0; q < P; ++q) {
+    part.files.push_back(p.out + "_" + r.pheno_names[q] + ".regenie" + (cm.multi ? ".part" + std::to_string(part.part) : (p.gz ? ".gz" : "")));
+    ofs.emplace_back(new TextOut(part.files.back(), cm.multi ? false : p.gz));
+    if (!*ofs.back()) throw std::runtime_error("cannot write file : " + part.files.back());
+    if (part.part == 0) *ofs.back() << "CHROM GENPOS ID ALLELE0 ALLELE1 A1FREQ " << (cm.show_info ? "INFO " : "") << "N TEST BETA SE CHISQ LOG10P EXTRA\n";
+  }
+  std::unique_ptr<BedAhead> bed(cm.in == In::Bed ? new BedAhead(cm) : nullptr);
+  std::unique_ptr<BgenAhead> bgen(cm.fast_bgen ? new BgenAhead(cm) : nullptr);
+  if (bgen) bgen->start();
+  int64_t n_ign[3] = {0, 0, 0};      // ignored variants, ignored tests, tests
+  double ms_device = 0, ms_format = 0;
+  int block = 0;
+  for (int chrom : r.chr_read) {
+    if (!cm.chr_snps.count(chrom)) continue;
+    const std::vector<int64_t>& snps = cm.chr_snps.at(chrom);
+    const int nb_chr = (int)((snps.size() + p.bsize - 1) / p.bsize);
+    if (block + nb_chr <= part.blk_lo || block >= part.blk_hi) { block += nb_chr; continue; }     // none of the chromosome's blocks is this part's
+    sout << "Chromosome " << chrom << " [" << nb_chr << " blocks in total]\n";
+    null.set_up(chrom, s2);
     for (int bb = 0; bb < nb_chr; ++bb, ++block) {
       if (block < part.blk_lo || block >= part.blk_hi) continue;
       const int64_t j0 = (int64_t)bb * p.bsize;
       const int bs = (int)std::min<int64_t>(p.bsize, (int64_t)snps.size() - j0);
-      sout << " block [" << block + 1 << "/" << total_blocks << "] : ";
+      sout << " block [" << block + 1 << "/" << cm.total_blocks << "] : ";
       auto t1 = std::chrono::steady_clock::now();
-      vidx.resize(bs);
-      for (int j = 0; j < bs; ++j) vidx[j] = r.snp_offset[snps[j0 + j]];
-      if (in != In::Dosage) rows.resize((size_t)bs * r.bpr);
-      std::unique_lock<std::mutex> rlk(g_reader_mu, std::defer_lock);
-      if (multi && in != In::Bed) rlk.lock();
-      DosPrep* dp = nullptr;
-      int dp_row0 = 0;                 // the block's first row in its prepared group
-      if (fast_bgen) {
-        if (rlk.owns_lock()) rlk.unlock();      // (the prepared block took the reader's lock itself)
-        auto tw = std::chrono::steady_clock::now();
-        const size_t gi = block_group[my_next].first;
-        dp_row0 = block_group[my_next].second;
-        DosPrep& d = preps[gi & 1];
-        if (groups[gi].first_block == my_next) {      // first block of its group: the group has to be ready, the next one is started
-          if (prep_ahead.valid()) prep_ahead.get();
-          else prepare(groups[gi].ref, d, (int)(gi & 1), (int64_t)gi);
-          if (gi + 1 < groups.size())
-            prep_ahead = std::async(std::launch::async, [&, nx = gi + 1]() { prepare(groups[nx].ref, preps[nx & 1], (int)(nx & 1), (int64_t)nx); });
-          if (!d.err.empty()) { if (prep_ahead.valid()) prep_ahead.wait(); throw std::runtime_error(d.err); }
-          ms_inflate += d.ms_inflate; ms_walk += d.ms_walk; ms_prep_wall += d.ms_wall;
-          if (d.dev_rows > 0) { ms_dev_read += d.ms_read; ms_dev_decode += d.ms_dev; }
-        }
-        ++my_next;
-        ms_prep_wait += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-        if (dp_row0 < d.dev_rows) ++n_dev_blocks; else ++n_host_blocks;
-        if (d.integral) dp = &d;
+      blk.begin(bs);
+      blk.vidx.resize(bs);
+      for (int j = 0; j < bs; ++j) blk.vidx[j] = r.snp_offset[snps[j0 + j]];
+      // fetch the genotypes
+      const PreparedBlock* pb = nullptr;
+      {
+        std::unique_lock<std::mutex> rlk(g_reader_mu, std::defer_lock);
+        if (cm.multi && cm.in != In::Bed && !bgen) rlk.lock();      // (the read-ahead's calls only read the handle)
+        if (bgen && !(pb = bgen->next_block())->integral) pb = nullptr;
+        if (cm.in == In::PgenHard) blk.read_pgen_hard();
+        else if (cm.in == In::Dosage && !pb) blk.read_dosage_rows();
       }
-      if (in == In::PgenHard) {   // ReadHardcalls per variant (Geno.cpp:2570-2573), as .bed-coded rows (00 = two ALT copies)
-        if (rg_pgen_read_bed_rows(r.pgen, bs, vidx.data(), rows.data(), r.bpr) != RG_PGEN_OK) throw std::runtime_error(rg_pgen_last_error(r.pgen));
-      } else if (in == In::Dosage && !dp) {
-        dbuf.resize((size_t)bs * r.n_file);
-        if (r.bgenh) {            // parseSnpfromBGEN (Geno.cpp:2186-2330): dosages and the terms of the IMPUTE info score
-          ibuf.resize((size_t)bs * r.n_file);
-          if (rg_bgen_read_dosages_info(r.bgenh, bs, vidx.data(), p.ref_first ? 1 : 0, dbuf.data(), ibuf.data(), r.n_file) != RG_BGEN_OK)
-            throw std::runtime_error(rg_bgen_last_error(r.bgenh));
-        } else if (rg_pgen_read_dosage_rows(r.pgen, bs, vidx.data(), dbuf.data(), r.n_file) != RG_PGEN_OK)   // Read() (Geno.cpp:2570-2571)
-          throw std::runtime_error(rg_pgen_last_error(r.pgen));
-      }
-      if (rlk.owns_lock()) rlk.unlock();
-      if (in == In::Bed) {   // the block's rows: read ahead by the previous iteration when it could be (same chromosome), else read now
-        if (ahead.valid()) { ahead.get(); rows.swap(rows_ahead); }
-        else read_bed(snps, j0, bs, rows);
-        if (bb + 1 < nb_chr && block + 1 < part.blk_hi) {
-          const int64_t jn = (int64_t)(bb + 1) * p.bsize;
-          const int bn = (int)std::min<int64_t>(p.bsize, (int64_t)snps.size() - jn);
-          ahead = std::async(std::launch::async, [&, jn, bn]() { read_bed(snps, jn, bn, rows_ahead); });
-        }
+      if (bed) {
+        const int64_t jn = j0 + bs;
+        blk.rows = bed->take(snps, j0, bs, (bb + 1 < nb_chr && block + 1 < part.blk_hi) ? (int)std::min<int64_t>(p.bsize, (int64_t)snps.size() - jn) : 0);
       }
       auto t_dev = std::chrono::steady_clock::now();
-      std::vector<double> total(bs, 0.0);
-      std::vector<int64_t> ns1(bs, 0);
-      std::vector<double> af_t, mac_t, info_num, info_t;   // per trait: only filled when some sample is masked for some trait
-      std::vector<int64_t> ns_t;
-      std::vector<uint8_t> variant_ignored(bs, 0);
-      rg_s2_qt_out o;
-      stats.resize((size_t)bs * P); bhat.resize((size_t)bs * P); sfac.resize(bs); ign.resize(bs);
-      memset(&o, 0, sizeof(o));
-      o.stats = stats.data(); o.bhat = bhat.data(); o.scale_fac = sfac.data(); o.ignored = ign.data();
-      test_ignored.assign((size_t)bs * P, 0);
-      bool integral = false;
-      const int dscale = r.bgenh ? 255 : 16384;
-      const uint16_t* g16p = nullptr;
-      int64_t g16ld = n;
-      int g16_on_device = 0;
-      if (dp) {      // the block the host threads prepared ahead
-        const size_t r0 = (size_t)dp_row0;
-        total.assign(dp->total.begin() + r0, dp->total.begin() + r0 + bs); ns1.assign(dp->ns1.begin() + r0, dp->ns1.begin() + r0 + bs);
-        info_num.assign(dp->info_num.begin() + r0, dp->info_num.begin() + r0 + bs);
-        variant_ignored.assign(dp->ignored.begin() + r0, dp->ignored.begin() + r0 + bs);
-        if (any_missing || glm) {
-          af_t.assign(dp->af_t.begin() + r0 * P, dp->af_t.begin() + (r0 + bs) * P); ns_t.assign(dp->ns_t.begin() + r0 * P, dp->ns_t.begin() + (r0 + bs) * P);
-          info_t.assign(dp->info_t.begin() + r0 * P, dp->info_t.begin() + (r0 + bs) * P);
-        }
-        const bool on_dev = dp_row0 < dp->dev_rows;      // (a group is split at a block boundary)
-        integral = true; g16ld = on_dev ? dp->ld_dev : ld16;
-        g16p = on_dev ? dp->g16_dev + r0 * (size_t)g16ld : dp->g16 + (r0 - (size_t)dp->host_row0) * (size_t)g16ld;
-        g16_on_device = on_dev ? 1 : 0;
-      } else if (in == In::Dosage) {
-        // dosages: the analysed samples' doubles, allele totals, the info-score numerator and the per-trait corrections on the host
-        // (parseSnpfromBGEN / readChunkFromPGENFileToG with update_trait_counts, Geno.cpp:2948-2959), the test on the fp64 route
-        G.assign((size_t)bs * n, 0.0);
-        info_num.assign(bs, 0.0);
-        if (any_missing || glm) { af_t.assign((size_t)bs * P, 0.0); ns_t.assign((size_t)bs * P, 0); info_t.assign((size_t)bs * P, 0.0); }
-        parallel_for(bs, nthreads, [&](int j) {
-          const double* d = dbuf.data() + (size_t)j * r.n_file;
-          const double* iv = r.bgenh ? ibuf.data() + (size_t)j * r.n_file : nullptr;
-          double* g = G.data() + (size_t)j * n;
-          double tot = 0.0, inf = 0.0; int64_t ns = 0;
-          for (int64_t k = 0; k < n; ++k) {
-            const int64_t i = file_idx[k];
-            const double v = d[i];
-            g[k] = v;
-            if (v == -3.0) continue;
-            const double e = iv ? iv[i] : v * v;
-            tot += v; inf += e; ++ns;
-            if ((any_missing || glm) && has_missing[k])
-              for (int q = 0; q < P; ++q)
-                if (!Mc[(size_t)q * n + k]) { af_t[(size_t)j * P + q] -= v; ns_t[(size_t)j * P + q] -= 1; info_t[(size_t)j * P + q] -= e; }
-          }
-          total[j] = tot; ns1[j] = ns; info_num[j] = inf;
-          if (std::min(tot, 2.0 * ns - tot) < p.min_mac) variant_ignored[j] = 1;      // compute_mac (Geno.cpp:3077-3108), autosomes
-        });
-        // 8-bit .bgen probabilities and .pgen dosages are integers in units of 1 / 255 and 1 / 16384: as uint16 rows they take the
-        // integer route of the library (digit planes on the i8 matrix cores, 2 B per genotype over PCIe); anything else, or
-        // RG_S2_DENSE=1, the fp64 route
-        integral = !dense_route || glm;
-        if (integral) {
-          G16.resize((size_t)bs * n);
-          std::vector<uint8_t> bad(bs, 0);
-          parallel_for(bs, nthreads, [&](int j) {
-            const double* g = G.data() + (size_t)j * n;
-            uint16_t* q = G16.data() + (size_t)j * n;
-            for (int64_t k = 0; k < n; ++k) {
-              if (g[k] == -3.0) { q[k] = 0xFFFFu; continue; }
-              const double v = g[k] * dscale, rv = std::nearbyint(v);
-              if (std::fabs(v - rv) > 1e-6 || rv < 0 || rv > 2.0 * dscale) { bad[j] = 1; break; }
-              q[k] = (uint16_t)rv;
-            }
-          });
-          for (int j = 0; j < bs; ++j) if (bad[j]) integral = false;
-          g16p = G16.data();
-        }
-      }
-      std::vector<double> af_d; std::vector<int64_t> ns_d;
-      if (glm && in == In::Dosage) { af_d = af_t; ns_d = ns_t; }
-      if (glm) {
-        // the score test of the block through the C ABI (rg_s2_bt_score_*: contractions on the i8 matrix cores, C x C algebra in the library):
-        // hard calls as packed rows, dosages as integer rows
-        bt_counts.resize((size_t)bs * 4); bt_vstat.resize((size_t)bs * 4);
-        denum_v.assign((size_t)bs * P, 0.0);
-        std::vector<double> mu_v(bs, 0.0), totp((size_t)bs * P, 0.0);
-        std::vector<uint8_t> sparse_v(bs, 0);
-        std::vector<int32_t> nobsp((size_t)bs * P, 0);
-        rg_s2_bt_out bo;
-        memset(&bo, 0, sizeof(bo));
-        bo.stats = stats.data(); bo.bhat = bhat.data(); bo.denum = denum_v.data(); bo.test_ignored = test_ignored.data(); bo.mean = mu_v.data();
-        bo.ignored = ign.data(); bo.sparse = sparse_v.data();
-        const uint8_t* src = rows.data();
-        int64_t ld = r.bpr;
-        if (in == In::Dosage) {
-          if (!integral) throw std::runtime_error("--step 2 --bt / --ct on dosages that are not integer multiples of 1/" + std::to_string(dscale) + " is not built.");
-          bo.vstat = bt_vstat.data();
-          s2check(rg_s2_bt_score_int(s2, g16p, g16ld, bs, g16_on_device, dscale, NUMTOL, &bo));
-        } else {
-          if (!identity) {
-            ld = (n + 3) / 4;
-            packed.assign((size_t)bs * ld, 0);
-            parallel_for(bs, nthreads, [&](int j) {
-              const uint8_t* row = rows.data() + (size_t)j * r.bpr;
-              uint8_t* dst = packed.data() + (size_t)j * ld;
-              for (int64_t k = 0; k < n; ++k) {
-                const int64_t i = file_idx[k];
-                dst[k >> 2] |= (uint8_t)(((row[i >> 2] >> (2 * (i & 3))) & 3) << (2 * (k & 3)));
-              }
-            });
-            src = packed.data();
-          }
-          bo.counts = bt_counts.data(); bo.total_p = totp.data(); bo.n_obs_p = nobsp.data();
-          s2check(rg_s2_bt_score_packed(s2, src, ld, bs, 0, flip, NUMTOL, &bo));
-        }
-        af_t.assign((size_t)bs * P, 0.0); ns_t.assign((size_t)bs * P, 0);
-        for (int j = 0; j < bs; ++j) {
-          if (in != In::Dosage) {     // (dosages: the host loop above has them, summed as the reference sums)
-            const double n1 = bt_counts[(size_t)j * 4], n2 = bt_counts[(size_t)j * 4 + 1], nm = bt_counts[(size_t)j * 4 + 2];
-            ns1[j] = (int64_t)((double)n - nm); total[j] = n1 + 2.0 * n2;
-          }
-          sfac[j] = 1.0;
-          if (std::min(total[j], 2.0 * ns1[j] - total[j]) < p.min_mac) variant_ignored[j] = 1;
-          for (int q = 0; q < P; ++q) {
-            af_t[(size_t)j * P + q] = in != In::Dosage ? totp[(size_t)j * P + q] : af_d[(size_t)j * P + q];      // per-trait allele and sample counts
-            ns_t[(size_t)j * P + q] = in != In::Dosage ? (int64_t)nobsp[(size_t)j * P + q] : ns_d[(size_t)j * P + q];
-          }
-        }
-        if (correct) {
-          // check_pval_snp (Step2_Models.cpp:1987-2029): |z| above the threshold -> run_SPA_test (--spa) or fit_firth_logistic_snp_fast on Gres / Gamma_sqrt
-          // with the null Firth model's covariate effects in the offset.  The flagged (variant, trait) pairs are re-tested on the device, one
-          // workgroup per pair (rg_s2_bt_correct); the exact Firth test (--firth without --approx: a C + 1 parameter fit) stays on the host threads.
-          corrected.assign((size_t)bs * P, 0); corr_fail.assign((size_t)bs * P, 0);
-          corr_beta.assign((size_t)bs * P, 0.0); corr_se.assign((size_t)bs * P, 0.0); corr_chisq.assign((size_t)bs * P, 0.0); corr_logp.assign((size_t)bs * P, -1.0);
-          std::vector<int> todo;
-          for (int j = 0; j < bs; ++j)
-            for (int q = 0; q < P; ++q)
-              if (!variant_ignored[j] && !ign[j] && !test_ignored[(size_t)j * P + q] && std::fabs(stats[(size_t)j * P + q]) > z_thr) todo.push_back(j * P + q);
-          if (spa || p.firth_approx) {
-            std::vector<int32_t> pv_(todo.size()), pt_(todo.size());
-            std::vector<uint8_t> pf_(todo.size());
-            for (size_t t = 0; t < todo.size(); ++t) {
-              const int j = todo[t] / P, q = todo[t] % P;
-              pv_[t] = j; pt_[t] = q;
-              if (spa) pf_[t] = sparse_v[j];                                                            // fastSPA (Step2_Models.cpp:2087-2097)
-              else {
-                const double tq = total[j] + af_t[(size_t)j * P + q];
-                const double nsq = (double)(ns1[j] + ns_t[(size_t)j * P + q]);
-                pf_[t] = sparse_v[j] && std::min(tq, 2.0 * nsq - tq) < 50.0;                            // fit_firth_logistic_snp_fast :1173-1185: carriers only
-              }
-            }
-            std::vector<rg_s2_bt_corr> cr(todo.size());
-            s2check(rg_s2_bt_correct(s2, spa ? RG_S2_BT_SPA : RG_S2_BT_FIRTH_APPROX, (int32_t)todo.size(), pv_.data(), pt_.data(), pf_.data(), p.firth_se ? 1 : 0, cr.data()));
-            for (size_t t = 0; t < todo.size(); ++t) {
-              const size_t e = (size_t)todo[t];
-              corrected[e] = 1;
-              if (cr[t].fail) { corr_fail[e] = 1; continue; }
-              corr_beta[e] = cr[t].beta; corr_se[e] = cr[t].se; corr_chisq[e] = cr[t].chisq; corr_logp[e] = cr[t].logp;
-            }
-          } else
-          parallel_for((int)todo.size(), nthreads, [&](int t) {
-            const int j = todo[t] / P, q = todo[t] % P;
-            const double mu = mu_v[j];
-            std::vector<double> gt(n);                // the mean-imputed genotype of the analysed samples
-            if (in == In::Dosage) { const double* g = G.data() + (size_t)j * n; for (int64_t k = 0; k < n; ++k) gt[k] = g[k] == -3.0 ? mu : g[k]; }
-            else {
-              const uint8_t* row = src + (size_t)j * ld;
-              for (int64_t k = 0; k < n; ++k) {
-                double hc = lut[(row[k >> 2] >> (2 * (k & 3))) & 3];
-                if (flip && hc != -3.0) hc = 2.0 - hc;
-                gt[k] = hc == -3.0 ? mu : hc;
-              }
-            }
-            // the exact test (fit_firth_logistic_snp, Step2_Models.cpp:1062-1156): design [covariates | g~ on its raw scale], offset = the LOCO
-            // prediction; null fit = the variant's coefficient held at 0 under the same penalty, then every coefficient free
-            const uint8_t* mq = Mc.data() + (size_t)q * n;
-            std::vector<const double*> cols(C + 1);
-            for (int c = 0; c < C; ++c) cols[c] = Xc.data() + (size_t)c * n;
-            cols[C] = gt.data();
-            std::vector<double> bf(C + 1, 0.0), inv;
-            for (int c = 0; c < C; ++c) bf[c] = firth_bnull[(size_t)q * C + c];
-            double dev0 = 0.0, dev1 = 0.0;
-            corrected[(size_t)j * P + q] = 1;
-            const bool okx = firth_fit_cols(Yc.data() + (size_t)q * n, cols, mq, blup_off.data() + (size_t)q * n, n, C, 25.0, bf, &dev0) &&
-                             firth_fit_cols(Yc.data() + (size_t)q * n, cols, mq, blup_off.data() + (size_t)q * n, n, C + 1, 5.0, bf, &dev1, &inv);
-            const double lrt = dev0 - dev1;
-            if (!okx || lrt < 0) { corr_fail[(size_t)j * P + q] = 1; return; }
-            corr_beta[(size_t)j * P + q] = bf[C];
-            corr_chisq[(size_t)j * P + q] = lrt;
-            corr_se[(size_t)j * P + q] = (p.firth_se && lrt > 0) ? std::fabs(bf[C]) / std::sqrt(lrt) : std::sqrt(inv[(size_t)C * (C + 1) + C]);
-          });
-        }
-      } else if (in == In::Dosage) {
-        if (integral) s2check(rg_s2_qt_block_int(s2, g16p, g16ld, bs, g16_on_device, dscale, NUMTOL, &o));
-        else s2check(rg_s2_qt_block(s2, G.data(), n, bs, 0, NUMTOL, &o));
-      } else if (!dense_route) {
-        // hard calls stay packed: the 2-bit codes of the analysed samples go to the device as they are (the rows of the file itself
-        // when no sample was dropped), the library counts the calls and contracts them on the i8 matrix cores
-        const uint8_t* src = rows.data();
-        int64_t ld = r.bpr;
-        if (!identity) {
-          ld = (n + 3) / 4;
-          packed.assign((size_t)bs * ld, 0);
-          parallel_for(bs, nthreads, [&](int j) {
-            const uint8_t* row = rows.data() + (size_t)j * r.bpr;
-            uint8_t* dst = packed.data() + (size_t)j * ld;
-            for (int64_t k = 0; k < n; ++k) {
-              const int64_t i = file_idx[k];
-              dst[k >> 2] |= (uint8_t)(((row[i >> 2] >> (2 * (i & 3))) & 3) << (2 * (k & 3)));
-            }
-          });
-          src = packed.data();
-        }
-        mean_v.resize(bs); nobs_v.resize(bs);
-        o.mean = mean_v.data(); o.n_obs = nobs_v.data();
-        if (any_missing) {
-          totp_v.resize((size_t)bs * P); nobsp_v.resize((size_t)bs * P);
-          o.total_p = totp_v.data(); o.n_obs_p = nobsp_v.data();
-        }
-        s2check(rg_s2_qt_block_packed(s2, src, ld, bs, 0, flip, NUMTOL, &o));
-        if (any_missing) { af_t.assign((size_t)bs * P, 0.0); ns_t.assign((size_t)bs * P, 0); }
-        for (int j = 0; j < bs; ++j) {
-          ns1[j] = nobs_v[j];
-          total[j] = std::nearbyint(mean_v[j] * (double)nobs_v[j]);       // the allele count is an integer: mean = total / n_obs
-          if (std::min(total[j], 2.0 * ns1[j] - total[j]) < p.min_mac) variant_ignored[j] = 1;   // compute_mac (Geno.cpp:3077-3108), autosomes
-          if (any_missing)                                                  // update_trait_counts (Geno.cpp:2948-2959) as differences from the totals
-            for (int q = 0; q < P; ++q) {
-              af_t[(size_t)j * P + q] = std::nearbyint(totp_v[(size_t)j * P + q]) - total[j];
-              ns_t[(size_t)j * P + q] = (int64_t)nobsp_v[(size_t)j * P + q] - ns1[j];
-            }
-        }
-      } else {
-        // parseSnpfromBed: decode the analysed samples, allele counts
-        G.assign((size_t)bs * n, 0.0);
-        if (any_missing) { af_t.assign((size_t)bs * P, 0.0); mac_t.assign((size_t)bs * P, 0.0); ns_t.assign((size_t)bs * P, 0); }
-        parallel_for(bs, nthreads, [&](int j) {
-          const uint8_t* row = rows.data() + (size_t)j * r.bpr;
-          double* g = G.data() + (size_t)j * n;
-          double tot = 0.0; int64_t ns = 0;
-          for (int64_t k = 0; k < n; ++k) {
-            const int64_t i = file_idx[k];
-            double hc = lut[(row[i >> 2] >> (2 * (i & 3))) & 3];
-            if (flip && hc != -3.0) hc = 2.0 - hc;
-            g[k] = hc;
-            if (hc != -3.0) {
-              tot += hc; ++ns;
-              if (any_missing && has_missing[k])   // update_trait_counts (Geno.cpp:2948-2959): subtract from the totals of the traits the sample is masked for
-                for (int q = 0; q < P; ++q)
-                  if (!Mc[(size_t)q * n + k]) { af_t[(size_t)j * P + q] -= hc; mac_t[(size_t)j * P + q] -= hc; ns_t[(size_t)j * P + q] -= 1; }
-            }
-          }
-          total[j] = tot; ns1[j] = ns;
-          // compute_mac (Geno.cpp:3077-3108), autosomes
-          const double mac = std::min(tot, 2.0 * ns - tot);
-          if (mac < p.min_mac) variant_ignored[j] = 1;
-        });
-        s2check(rg_s2_qt_block(s2, G.data(), n, bs, 0, NUMTOL, &o));
-      }
-      // the result lines (compute_score_qt after the statistic, Step2_Models.cpp:440-466; print_sum_stats_single): formatted by the host threads
-      // in contiguous chunks of variants, appended to the files in order
+      BlockCounts bc(bs);
+      if (pb) blk.from_prepared(*pb, bc);
+      else if (cm.in == In::Dosage) blk.from_dosage_rows(bc);
+      else if (cm.glm || !cm.env.dense) blk.from_packed();
+      else blk.from_dense_bed(bc);
+      // score, correct, format
+      if (cm.glm) blk.score_glm(bc); else blk.score_qt(bc);
+      if (cm.glm && cm.correct) blk.correct(bc);
       auto t_fmt = std::chrono::steady_clock::now();
       ms_device += std::chrono::duration<double, std::milli>(t_fmt - t_dev).count();
-      const int nchunk = std::max(1, std::min(nthreads, bs / 64));
-      std::vector<std::string> chunk_out((size_t)nchunk * P);
-      std::vector<int64_t> c_snps(nchunk, 0), c_tests(nchunk, 0), c_tested(nchunk, 0);
-      parallel_for(nchunk, nchunk, [&](int t) {
-        for (int j = (int)((int64_t)bs * t / nchunk), je = (int)((int64_t)bs * (t + 1) / nchunk); j < je; ++j) {
-          if (!variant_ignored[j] && show_info && p.set_min_info && ns1[j] > 0) {   // the all-sample info score below --minINFO drops the variant (Geno.cpp:2349-2353)
-            const double af1 = total[j] / (2.0 * ns1[j]);
-            double info1 = 1.0;
-            if (af1 != 0.0 && af1 != 1.0)
-              info1 = r.bgenh ? 1.0 - info_num[j] / (2.0 * ns1[j] * af1 * (1.0 - af1)) : (info_num[j] / ns1[j] - 4.0 * af1 * af1) / (2.0 * af1 * (1.0 - af1));
-            if (info1 < p.min_info) variant_ignored[j] = 1;
-          }
-          if (variant_ignored[j] || ign[j]) { ++c_snps[t]; continue; }
-          const int64_t sj = snps[j0 + j];
-          std::ostringstream head;
-          head << r.snp_chrom[sj] << " " << r.snp_pos[sj] << " " << r.snp_ids[sj] << " " << r.snp_a0[sj] << " " << r.snp_a1[sj] << " ";
-          for (int q = 0; q < P; ++q) {
-            double af = total[j] / (2.0 * ns1[j]);
-            int64_t nsq = ns1[j];
-            double infq = show_info ? info_num[j] : 0.0;
-            if (test_ignored[(size_t)j * P + q]) continue;
-            if (any_missing || glm) {   // compute_mac / compute_aaf_info per trait
-              const double tq = total[j] + af_t[(size_t)j * P + q];
-              nsq = ns1[j] + ns_t[(size_t)j * P + q];
-              const double macq = std::min(tq, 2.0 * nsq - tq);
-              if (macq < p.min_mac) { ++c_tests[t]; continue; }
-              af = tq / (2.0 * nsq);
-              if (show_info) infq += info_t[(size_t)j * P + q];
-            }
-            double info = 1.0;     // compute_aaf_info (Geno.cpp:3132-3141): IMPUTE info for .bgen, MaCH r2 for .pgen dosages
-            if (show_info && af != 0.0 && af != 1.0)
-              info = r.bgenh ? 1.0 - infq / (2.0 * nsq * af * (1.0 - af)) : (infq / nsq - 4.0 * af * af) / (2.0 * af * (1.0 - af));
-            if (show_info && p.set_min_info && info < p.min_info) { ++c_tests[t]; continue; }     // ignored_trait (Geno.cpp:3143-3144)
-            const double st = stats[(size_t)j * P + q];
-            double bh = bhat[(size_t)j * P + q], se = bh / st, chisq = st * st;
-            bool test_fail = false;
-            double logp_spa = -1.0;
-            if (correct && corrected[(size_t)j * P + q]) {
-              if (corr_fail[(size_t)j * P + q]) test_fail = true;                    // get_sumstats(true, ...): the score test's BETA / SE, no p-value
-              else { bh = corr_beta[(size_t)j * P + q]; se = corr_se[(size_t)j * P + q]; chisq = corr_chisq[(size_t)j * P + q]; logp_spa = corr_logp[(size_t)j * P + q]; }
-            }
-            const double logp = logp_spa >= 0 ? logp_spa : get_logp(chisq);       // --spa prints the p-value it computed, the chi-square is derived from it
-            std::ostringstream ln;
-            if (af >= 0) ln << head.str() << af << " ";            // print_sum_stats_single (Step2_Models.cpp:2505-2518): a negative value is "NA"
-            else ln << head.str() << "NA ";
-            if (show_info) { if (info >= 0) ln << info << " "; else ln << "NA "; }      // (the IMPUTE score of very uncertain dosages can be negative)
-            ln << nsq << " ADD ";
-            if (se >= 0 && !std::isnan(se)) ln << bh << ' ' << se;
-            else ln << "NA NA";
-            if (chisq >= 0 && !std::isnan(logp) && !test_fail) ln << ' ' << chisq << ' ' << logp;
-            else ln << " NA NA";
-            ln << (test_fail ? " TEST_FAIL\n" : " NA\n");
-            chunk_out[(size_t)t * P + q] += ln.str();
-            ++c_tested[t];
-          }
-        }
-      });
-      for (int t = 0; t < nchunk; ++t) {
-        for (int q = 0; q < P; ++q) *ofs[q] << chunk_out[(size_t)t * P + q];
-        n_ignored_snps += c_snps[t]; n_ignored_tests += c_tests[t]; n_tested += c_tested[t];
-      }
-      ms_format += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fmt).count();
+      blk.format(bc, snps, j0, ofs, n_ign);
+      ms_format += ms_since(t_fmt);
       sout << "done (" << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t1).count() << "ms) \n";
     }
   }
-  cleanup.run();
-  if (bdev) {
-    if (getenv("RG_TIMING"))
-      fprintf(stderr, "[timing] step 2 part %d: BGEN on the device: %lld blocks (%lld on the host route) | reading the stored streams %.0f ms | copy + inflate + walk on the GPU %.0f ms (both overlapped with the tests of the previous block)\n",
-              part.part, (long long)n_dev_blocks, (long long)n_host_blocks, ms_dev_read, ms_dev_decode);
-    rg_bgen_dev_destroy(bdev);
-    bdev = nullptr;
-  }
-  if (getenv("RG_TIMING"))
+  BgenTiming bt;
+  if (bgen) { bgen->report_device(); bt = bgen->timing; bgen.reset(); }
+  if (cm.env.timing)
     fprintf(stderr, "[timing] step 2 part %d: host threads %d (read-ahead %d) | chromosome set-up %.0f ms | waiting for the prepared block %.0f ms (preparing: %.0f ms wall, overlapped; %.0f thread-ms inflate + %.0f thread-ms byte walk) | "
-            "upload + device + results %.0f ms | formatting + writing %.0f ms\n", part.part, nthreads, nt_prep, ms_chr, ms_prep_wait, ms_prep_wall, ms_inflate, ms_walk, ms_device, ms_format);
-  if (fd >= 0) close(fd);
+            "upload + device + results %.0f ms | formatting + writing %.0f ms\n", part.part, cm.nthreads, cm.nt_prep, null.ms_chr, bt.prep_wait, bt.prep_wall, bt.inflate, bt.walk, ms_device, ms_format);
   rg_s2_destroy(s2);
-  part.n_ignored_snps = n_ignored_snps; part.n_ignored_tests = n_ignored_tests;
-  part.firth_body = firth_file_body;
+  part.n_ignored_snps = n_ign[0]; part.n_ignored_tests = n_ign[1];
+  part.firth_body = null.firth_file_body;
   return 0;
 }
 

@@ -714,7 +714,7 @@ def test_cli_step2_multi_gpu(example_dir, tmp_path, mode):
         for k in (1, 2):
             assert open(str(tmp_path / ("one_%d.firth" % k))).read() == open(str(tmp_path / ("three_%d.firth" % k))).read()
     if mode == "bt_spa_bgen":
-        # the .bgen blocks reach the device through the read-ahead (inflate + one byte walk into 2-byte rows, driver_step2.cpp `prepare`); the
+        # the .bgen blocks reach the device through the read-ahead (inflate + one byte walk into 2-byte rows, driver_step2_bgen.cpp BgenAhead::prepare); the
         # general route (three double rows per variant, RG_S2_BGEN_ROWS=1) must print the same files
         rows = subprocess.run([BIN] + cmd + ["--out", "rows"], cwd=str(tmp_path), capture_output=True, text=True, timeout=300, env=dict(os.environ, RG_S2_BGEN_ROWS="1"))
         assert rows.returncode == 0, rows.stdout[-2000:] + rows.stderr[-2000:]
@@ -806,6 +806,52 @@ def test_cli_step2_qt_masked_phenotypes_against_reference_output(tmp_path, fmt):
     assert m and int(m.group(1)) > 0 and int(m.group(2)) > 0, r3.stderr[-2000:]
     for k in range(1, spec["P"] + 1):
         assert open(str(tmp_path / ("s2_Y%d.regenie" % k))).read() == keep[k]
+
+
+def test_cli_step2_bgen_error_with_read_ahead_in_flight(tmp_path):
+    """A flipped bit in the middle of one variant's stored stream, in the third group of the BGEN read-ahead (--bsize 40, groups of 80 variants):
+    the device decoder flags the stream, the host threads' route reports it as the reference does, and the run ends with that message while the
+    workers of the NEXT group are running -- promptly, with a non-zero status, and on three parts without a part file left behind."""
+    import gzip
+    import json
+    from oracle.bgen import BgenOracle
+    from tests.util import synth_dosages, write_plink, write_synth_bgen
+    R = os.path.join(ROOT, "tests", "golden", "ref_outputs")
+    meta = json.load(open(os.path.join(R, "qt_kfold_synth_missing", "meta.json")))
+    spec = meta["synthetic"]
+    S = str(tmp_path / "synth")
+    g = synth_dosages(spec["M"], spec["N"], miss_rate=spec.get("miss_rate", 0.0), seed=spec["seed"])
+    write_plink(S, g, spec["chroms"], P=spec["P"], seed=spec["seed"], binary=spec["binary"], missing_pheno=spec["missing_pheno"])
+    write_synth_bgen(S, g, spec["chroms"], seed=spec["seed"])
+    # the groups of a one-GPU run: consecutive blocks of 40 of one chromosome, two to a group
+    groups = []
+    chroms = list(spec["chroms"])
+    for c in sorted(set(chroms), key=chroms.index):
+        lo, m = chroms.index(c), chroms.count(c)
+        groups += [(lo + j0, min(80, m - j0)) for j0 in range(0, m, 80)]
+    assert len(groups) >= 5
+    hit = groups[2][0] + groups[2][1] // 2
+    bg = BgenOracle(S + ".bgen")
+    v = bg.variants[hit]
+    clen = int.from_bytes(bg.data[v["data"]:v["data"] + 4], "little")          # 4 bytes of inflated length + the stream
+    raw = bytearray(bg.data)
+    raw[v["data"] + 8 + (clen - 4) // 2] ^= 0x10
+    open(S + ".bgen", "wb").write(bytes(raw))
+    with open(str(tmp_path / "pred.list"), "w") as pl:
+        for k, nm in enumerate(meta["pred_list"]):
+            fn = str(tmp_path / ("ref_%d.loco" % (k + 1)))
+            open(fn, "wb").write(gzip.open(os.path.join(R, "qt_kfold_synth_missing", "out_%d.loco.gz" % (k + 1)), "rb").read())
+            pl.write("%s %s\n" % (nm, fn))
+    env = dict({k: v_ for k, v_ in os.environ.items() if k not in ("RG_S2_DENSE", "RG_S2_BGEN_ROWS", "RG_S2_BGEN_HOST")}, RG_S2_BGEN_GROUP="80")
+    args = [BIN, "--step", "2", "--bgen", S + ".bgen", "--sample", S + ".sample", "--phenoFile", S + ".pheno", "--covarFile", S + ".covar", "--bsize", "40", "--qt",
+            "--pred", str(tmp_path / "pred.list")]
+    message = "failed to decompress genotype data block for variant: " + v["rsid"]
+    for world, out in (([], "one"), (["--gpus", "3", "--single-device"], "three")):
+        r = subprocess.run(args + world + ["--out", out], cwd=str(tmp_path), capture_output=True, text=True, timeout=120, env=env)
+        assert r.returncode != 0, r.stdout[-2000:]
+        assert message in r.stdout + r.stderr, r.stdout[-2000:] + r.stderr[-2000:]
+        assert "block [3/" in r.stdout                                          # the groups before the damaged one were tested
+    assert not [fn for fn in os.listdir(str(tmp_path)) if ".part" in fn]
 
 
 def test_cli_step2_bt_score_test_against_reference_output(example_dir, tmp_path):

@@ -155,10 +155,32 @@ def test_the_driver_on_emulated_kernels_beside_regenie_itself(tmp_path, monkeypa
     monkeypatch.setattr(fz, "BIN", build_bt_step2_driver(str(tmp_path / "build")))
     for k, v in dict(FUZZ_ROUTES="bt_loocv", FUZZ_BT_STEP2="3", FUZZ_DRIVER="1", FUZZ_DRIVER_BT_ONLY="1", RG_S2_BGEN_ROWS="1").items():
         monkeypatch.setenv(k, v)
+    bgen_runs = []                                        # the driver's Step-2 commands on the BGEN file, as run_one issues them
+    real_run = subprocess.run
+
+    def recording_run(cmd, *a, **kw):
+        if cmd[0] == fz.BIN and "--bgen" in cmd:
+            bgen_runs.append((list(cmd), kw.get("cwd")))
+        return real_run(cmd, *a, **kw)
+    monkeypatch.setattr(subprocess, "run", recording_run)
     for seed in (3, 6):
         line, ok = fz.run_one(seed, str(tmp_path))
         assert ok, line
         assert "from BGEN dosages" in line
+        if seed != 3:
+            continue
+        # the same commands through the read-ahead's host route (BgenAhead without a device decoder: RG_S2_BGEN_HOST=1 and no RG_S2_BGEN_ROWS):
+        # the same files as the general dosage rows gave, byte for byte
+        assert len(bgen_runs) == 2, bgen_runs
+        for cmd, cwd in bgen_runs:
+            out = cmd[cmd.index("--out") + 1]
+            env = dict({k: v for k, v in os.environ.items() if k != "RG_S2_BGEN_ROWS"}, RG_S2_BGEN_HOST="1")
+            r = real_run(cmd[:cmd.index("--out")] + ["--out", out + "h"], cwd=cwd, capture_output=True, text=True, timeout=900, env=env)
+            assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+            mine = sorted(f for f in os.listdir(cwd) if f.startswith(out + "_") and f.endswith(".regenie"))
+            assert mine
+            for f in mine:
+                assert open(os.path.join(cwd, f), "rb").read() == open(os.path.join(cwd, out + "h" + f[len(out):]), "rb").read(), f
     monkeypatch.setenv("FUZZ_BT_STEP2", "4")             # and from a .pgen with a dosage track: the reader's zero count decides `sparse` (before the flip)
     line, ok = fz.run_one(5, str(tmp_path))
     assert ok and "from a .pgen with dosages" in line, line

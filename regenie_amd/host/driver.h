@@ -115,6 +115,10 @@ struct Params {
   double range_min = 0, range_max = 0;
   // --step 2 --compute-corr: the LD matrix of a region (Data::ld_comp, Data.cpp:3807-3848; driver_ld.cpp)
   bool compute_corr = false, corr_text = false, forcein_vars = false;
+  // --step 2 --condition-list FILE [--condition-file FORMAT,FILE [--condition-file-sample FILE]] [--max-condition-vars N]: the listed variants become
+  // covariates and leave the tested set (Regenie.cpp:217-219, :277, :516, :714-722; condition_variants in driver_inputs.cpp)
+  std::string condition_list, condition_fmt, condition_file, condition_sample;
+  uint32_t max_condition_vars = 10000;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards
@@ -234,6 +238,10 @@ struct Run {
   bool dosage_mode = false;              // --pgen with dosage tracks / --bgen: rows of doubles, level 0 from rg_l0_blocks_f64
   bool has_male = false;                 // a sample with sex code 1 in the .fam / .psam (Step 2 on chromosome X needs it)
   rg_bgen* bgenh = nullptr;              // --bgen: open reader
+  // --condition-list: the conditioning variants in ascending id order (filters->condition_snp_names is a std::map, Geno.cpp:4151-4179) with their
+  // index in the main genotype file (-1: not met among the variants the chromosome / range filter leaves)
+  std::map<std::string, int64_t> cond_snps;
+  int n_cond = 0;                        // columns appended to the covariates (not counted in the log's n_cov, as in the reference)
   Run() = default;
   Run(const Run&) = delete;
   ~Run() { if (pgen) rg_pgen_close(pgen); if (bgenh) rg_bgen_close(bgenh); }
@@ -332,6 +340,8 @@ void read_bgen_meta(Run& r);
 void read_bim_fam(Run& r);
 void apply_sample_and_variant_filters(Run& r);
 void blup_read(Run& r, const std::unordered_map<std::string, int64_t>& idx);
+void read_condition_list(Run& r);
+void condition_variants(Run& r, const std::vector<uint8_t>& in_cov, std::vector<double>& Xraw, int& ncols);
 void read_pheno_cov(Run& r);
 void prep_parallel_l0(Run& r);
 void prep_parallel_l1(Run& r, int total_n_block, int64_t n_variants);

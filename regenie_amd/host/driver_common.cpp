@@ -359,6 +359,15 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--ld-extract") { need(i); usage_error("--ld-extract (burden masks in the LD matrix) is not built: use --extract [--forcein-vars] for single variants."); }
     else if (a == "--skip-scaleG") usage_error("--skip-scaleG (the LD matrix of unscaled genotypes) is not built.");
     else if (a == "--sparse-thr") { need(i); usage_error("--sparse-thr (the sparsified LD matrix, which needs --skip-scaleG) is not built."); }
+    else if (a == "--condition-list") p.condition_list = need(i);                              // Regenie.cpp:217, :516
+    else if (a == "--condition-file") {                                                      // Regenie.cpp:714-722
+      auto t = split_char(need(i), ',');
+      if (t.size() != 2) usage_error("invalid option input for --condition-file");
+      if (t[0] != "bed" && t[0] != "bgen" && t[0] != "pgen") usage_error("invalid file format for --condition-file (either bed/bge/pgen)");
+      p.condition_fmt = t[0]; p.condition_file = t[1];
+    }
+    else if (a == "--condition-file-sample") p.condition_sample = need(i);                    // Regenie.cpp:219
+    else if (a == "--max-condition-vars") p.max_condition_vars = (uint32_t)std::strtoul(need(i).c_str(), nullptr, 10);   // Regenie.cpp:277
     else if (a == "--chr") { const std::string v = need(i); saw_chr.push_back(v); }           // Regenie.cpp:650-655
     else if (a == "--chrList") { for (auto& s : split_char(need(i), ',')) saw_chr.push_back(s); }   // Regenie.cpp:643-649
     else if (a == "--range") {                                                                // Regenie.cpp:741-755
@@ -395,6 +404,27 @@ Params parse_args(int argc, char** argv) {
   if (p.set_range) {
     p.range_chr = chr_str_to_int(range_chr_str, p.nchrom);
     if (p.range_chr <= 0) usage_error("unrecognized chromosome in --range.");          // Regenie.cpp:1153-1154
+  }
+  if (!p.condition_fmt.empty() && p.condition_list.empty()) usage_error("must use --condition-list if using --condition-file.");      // Regenie.cpp:1159-1160
+  if (!p.condition_sample.empty() && p.condition_fmt != "bgen") usage_error("--condition-file-sample goes with --condition-file bgen,FILE.");
+  if (!p.condition_list.empty()) {
+    if (p.step != 2) usage_error("--condition-list in step 1 (conditioning the ridge regression on variants) is not built: it applies to the tests of step 2.");
+    auto check_file = [](const std::string& f, const char* opt) {                              // check_file, Regenie.cpp:1418-1436
+      if (f.empty()) usage_error(std::string("Invalid argument (=' ') specified for option --") + opt);
+      if (!file_exists(f)) usage_error(f + " doesn't exist for option --" + opt);
+    };
+    check_file(p.condition_list, "condition-list");                                            // Regenie.cpp:1350-1363
+    if (p.condition_fmt == "bgen") {
+      check_file(p.condition_file, "condition-file");
+      if (!p.condition_sample.empty()) check_file(p.condition_sample, "condition-file-sample");
+    } else if (!p.condition_fmt.empty()) {
+      if (p.condition_file.empty()) usage_error("Invalid file argument (=' ') specified for option --condition-file");
+      const bool bed = p.condition_fmt == "bed";
+      const std::string sufs[3] = {bed ? ".bed" : ".pgen", bed ? ".bim" : ".pvar", bed ? ".fam" : ".psam"};
+      for (int k = 0; k < 3; ++k)      // the text files may be gzipped, the genotype file may not
+        if (!file_exists(p.condition_file + sufs[k]) && (k == 0 || !file_exists(p.condition_file + sufs[k] + ".gz")))
+          usage_error(p.condition_file + sufs[k] + " doesn't exist for option --condition-file");
+    }
   }
   if (p.compute_corr) {          // Regenie.cpp:522-535
     if (p.step != 2) usage_error("--compute-corr / --output-corr-text need --step 2.");

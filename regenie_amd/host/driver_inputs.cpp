@@ -3,9 +3,51 @@
 
 namespace rgdrv {
 
+// get_conditional_vars (Geno.cpp:4151-4179): the first token of every line of --condition-list; a std::map, so duplicates collapse and the
+// variants -- the covariate columns later -- come in ascending id order, not in file order.  The list also joins the --exclude files.
+void read_condition_list(Run& r) {
+  const Params& p = r.p;
+  if (p.condition_list.empty()) return;
+  TextIn f(p.condition_list);
+  if (!f) throw std::runtime_error("cannot open file : " + p.condition_list);
+  std::string line;
+  while (std::getline(f, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    Tok t[1];
+    if (tokenize(line.data(), line.data() + line.size(), t, 1) < 1) throw std::runtime_error("incorrectly formatted file (" + p.condition_list + ")");
+    r.cond_snps[std::string(t[0].b, t[0].e)] = -1;
+  }
+  if (r.cond_snps.size() > p.max_condition_vars)
+    throw std::runtime_error("number of variants used for conditional analysis is greater than maximum of " + std::to_string(p.max_condition_vars) + " (otherwise use --max-condition-vars)");
+  if (r.cond_snps.empty()) throw std::runtime_error("no variants for conditional analysis given in file " + p.condition_list);
+}
+
+// A variant of the main genotype file that --condition-list names: it leaves the tested set like an --exclude'd one; without --condition-file its
+// position in the file is kept, if the --chr / --range filter lets it through (get_snps_offset looks it up among the variants read_bim kept,
+// Geno.cpp:1136-1137, :582-587).  Returns whether the variant is one of the list.
+static bool condition_take(Run& r, const std::string& vid, int64_t file_idx, int chrom, double pos) {
+  if (r.cond_snps.empty()) return false;
+  auto it = r.cond_snps.find(vid);
+  if (it == r.cond_snps.end()) return false;
+  const Params& p = r.p;
+  const bool pass = (p.chr_keep.empty() || p.chr_keep.count(chrom)) && (!p.set_range || (chrom == p.range_chr && pos >= p.range_min && pos <= p.range_max));
+  if (pass && it->second < 0) it->second = file_idx;
+  return true;
+}
+
+// get_snps_offset (Geno.cpp:4181-4199): without --condition-file every listed variant must be in the main genotype file
+static void condition_check_found(const Run& r) {
+  if (r.cond_snps.empty() || !r.p.condition_fmt.empty()) return;
+  size_t found = 0;
+  for (auto& kv : r.cond_snps) found += kv.second >= 0;
+  if (found == 0) throw std::runtime_error("none of the variants were found in the genotype file");
+  if (found != r.cond_snps.size()) throw std::runtime_error(std::to_string(r.cond_snps.size() - found) + " of the variants could not be found in the genotype file");
+}
+
 // prep_bgen (Geno.cpp:38-175): variant list from the file itself, sample identifiers embedded or from --sample
 void read_bgen_meta(Run& r) {
   const Params& p = r.p;
+  read_condition_list(r);
   sout << std::left << std::setw(20) << " * bgen" << ": [" << p.bgen << "]\n";
   if (rg_bgen_open(&r.bgenh, p.bgen.c_str()) != RG_BGEN_OK) {
     const std::string msg = rg_bgen_last_error(r.bgenh);
@@ -38,6 +80,7 @@ void read_bgen_meta(Run& r) {
     bool keep = true;
     if (!extract_files.empty() && !ext.count(rsid)) keep = false;
     if (!exclude_files.empty() && exc.count(rsid)) keep = false;
+    if (condition_take(r, rsid, j, c, (double)position)) keep = false;
     if (keep) {
       r.snp_chrom.push_back(c); r.snp_offset.push_back(j); r.snp_ids.push_back(rsid);
       if (p.step == 2 || p.set_range) {   // prep_bgen (Geno.cpp:80-86): allele0 is the file's second allele unless --ref-first ("switch so allele0 is ALT")
@@ -49,7 +92,8 @@ void read_bgen_meta(Run& r) {
   }
   sout << "   -n_snps = " << nv << "\n";
   if (!extract_files.empty()) sout << "   -keeping variants specified by --extract\n";
-  if (!exclude_files.empty()) sout << "   -removing variants specified by --exclude\n";
+  condition_check_found(r);
+  if (!exclude_files.empty() || !r.cond_snps.empty()) sout << "   -removing variants specified by --exclude\n";
   if (r.snp_chrom.empty()) throw std::runtime_error("no variant left to include in analysis.");
   if (r.snp_chrom.size() > 1000000 && !p.force_step1)
     throw std::runtime_error("it is not recommened to use more than 1M variants in step 1 (use --force-step1 to override)");
@@ -97,6 +141,7 @@ void read_bgen_meta(Run& r) {
 void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pgen: read_pvar / read_psam, Geno.cpp:771-1004
   const Params& p = r.p;
   if (!p.bgen.empty()) { read_bgen_meta(r); return; }
+  read_condition_list(r);
   const bool pg = !p.pgen.empty();
   std::future<void> fam_task;     // the .fam file is read on its own thread while this one reads the .bim (two 500,000-line files at BASELINE configs[2])
   std::string fam_fn;
@@ -216,6 +261,10 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
       bool keep = true;
       if (!extract_files.empty() && !ext.count(vid)) keep = false;
       if (!exclude_files.empty() && exc.count(vid)) keep = false;
+      if (!r.cond_snps.empty()) {
+        const size_t pc = pg ? pos_col : 3;
+        if (condition_take(r, vid, lineno, c, pc < t.size() ? (double)std::strtoul(t[pc].c_str(), nullptr, 0) : 0.0)) keep = false;
+      }
       if (keep) {
         r.snp_chrom.push_back(c); r.snp_offset.push_back(lineno); r.snp_ids.push_back(vid);
         if (!pg && (p.step == 2 || p.set_range)) {   // read_bim (Geno.cpp:546-553): the reference allele is the LAST one unless --ref-first
@@ -239,9 +288,10 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
     }
     sout << head.str() << "n_snps = " << lineno << "\n";
     if (!extract_files.empty()) sout << "   -keeping variants specified by --extract\n";
-    if (!exclude_files.empty()) sout << "   -removing variants specified by --exclude\n";
+    condition_check_found(r);
+    if (!exclude_files.empty() || !r.cond_snps.empty()) sout << "   -removing variants specified by --exclude\n";
     if (r.snp_chrom.empty()) throw std::runtime_error("no variant left to include in analysis.");
-    if (!extract_files.empty() || !exclude_files.empty())
+    if (!extract_files.empty() || !exclude_files.empty() || !r.cond_snps.empty())
       sout << "   -number of variants remaining in the analysis = " << r.snp_chrom.size() << "\n";
   }
   if (p.step == 1 && r.snp_chrom.size() > 1000000 && !p.force_step1)  // Data.cpp:173-175
@@ -402,6 +452,240 @@ void blup_read(Run& r, const std::unordered_map<std::string, int64_t>& idx) {
     if (!errs[q].empty()) throw std::runtime_error(errs[q]);
     sout << logs[q];
   }
+}
+
+// ---- --condition-list: the conditioning variants as covariate columns (extract_condition_snps, Pheno.cpp:952-983) --------------------------
+// .bed byte -> calls of four samples (buildLookupTable, Geno.cpp:2833-2856): 00 -> 2, 01 -> missing (-3), 10 -> 1, 11 -> 0 copies of the first .bim allele
+static inline double bed_call(const uint8_t* row, int64_t i) {
+  static const double code[4] = {2.0, -3.0, 1.0, 0.0};
+  return code[(row[i >> 2] >> (2 * (i & 3))) & 3];
+}
+
+static void read_bed_row(const std::string& fn, int64_t variant, int64_t bpr, std::vector<uint8_t>& row) {
+  std::ifstream f(fn, std::ios::binary);
+  if (!f) throw std::runtime_error("cannot open file : " + fn);
+  unsigned char magic[3] = {0, 0, 0};
+  f.read((char*)magic, 3);
+  if (magic[0] != 0x6c || magic[1] != 0x1b || magic[2] != 0x01) throw std::runtime_error("incorrect magic number in bed file.");
+  row.assign((size_t)bpr, 0);
+  f.seekg(3 + variant * bpr);
+  f.read((char*)row.data(), bpr);
+  if (f.gcount() != bpr) throw std::runtime_error("cannot read variant " + std::to_string(variant) + " of file : " + fn);
+}
+
+// One variant of the MAIN genotype file over the samples of the run (file order, --keep / --remove applied), -3 = missing, counting the allele the
+// tests count: read_snp_bed / read_snp_pgen / read_snp_bgen (Geno.cpp:3998-4089).  --ref-first applies to .bed and BGEN, not to .pgen.
+static void read_main_variant(Run& r, int64_t variant, std::vector<double>& g) {
+  const Params& p = r.p;
+  const int64_t N = r.N, nf = r.n_file;
+  g.assign((size_t)N, 0.0);
+  std::vector<double> full;
+  if (!p.bed.empty()) {
+    std::vector<uint8_t> row;
+    read_bed_row(p.bed + ".bed", variant, r.bpr, row);
+    full.resize((size_t)nf);
+    for (int64_t i = 0; i < nf; ++i) {
+      const double hc = bed_call(row.data(), i);
+      full[i] = (p.ref_first && hc != -3) ? 2 - hc : hc;
+    }
+  } else if (r.pgen) {
+    full.resize((size_t)nf);
+    const int rc = r.dosage_mode ? rg_pgen_read_dosages(r.pgen, variant, full.data()) : rg_pgen_read_hardcalls(r.pgen, variant, full.data());
+    if (rc != RG_PGEN_OK) throw std::runtime_error(rg_pgen_last_error(r.pgen));
+  } else {
+    full.resize((size_t)nf);
+    if (rg_bgen_read_dosages(r.bgenh, 1, &variant, p.ref_first ? 1 : 0, full.data(), nf) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(r.bgenh));
+  }
+  int64_t k = 0;
+  for (int64_t i = 0; i < nf; ++i)
+    if (!r.ind_ignore[i]) g[k++] = full[i];
+}
+
+// The variants of a second genotype file (extract_from_genofile("conditional", ...), Geno.cpp:4217-4286): its samples are matched to the run's by
+// FID_IID and only those with covariate data are read (read_fam / read_psam / setup_bgen, Geno.cpp:693-732, :1015-1068, :4289-4364); the calls
+// are the file's own -- first .bim allele, ALT of the .pgen, first allele of the BGEN file -- whatever --ref-first says ("does not matter ...
+// since used as covar", Geno.cpp:4528).  cols: N doubles per variant, -3 where the file has no call for a sample of the run.
+static void read_condition_file(Run& r, const std::vector<uint8_t>& in_cov, std::vector<double>& cols) {
+  const Params& p = r.p;
+  const int64_t N = r.N;
+  const std::string& pre = p.condition_file;
+  const bool bed = p.condition_fmt == "bed", pg = p.condition_fmt == "pgen";
+  auto open_text = [](const std::string& base) {      // the text files may be gzipped (Geno.cpp:623, :701)
+    return file_exists(base) ? base : base + ".gz";
+  };
+  rg_pgen* pgh = nullptr;
+  rg_bgen* bgh = nullptr;
+  struct Closer { rg_pgen*& a; rg_bgen*& b; ~Closer() { if (a) rg_pgen_close(a); if (b) rg_bgen_close(b); } } closer{pgh, bgh};
+  std::map<std::string, int64_t> index;      // variant id -> position in the file; a repeated id keeps its last position (index_map[id] = ...)
+  std::vector<std::string> fids;             // FID_IID of the file's samples
+  if (bed || pg) {
+    sout << "      -extracting variants using " << (bed ? "BED" : "PGEN") << " file prefix [" << pre << "]\n";
+    const std::string kind = bed ? "bim" : "pvar";
+    const std::string vfn = open_text(pre + "." + kind);
+    TextIn f(vfn);
+    if (!f) throw std::runtime_error("cannot open file : " + vfn);
+    std::string line;
+    size_t id_col = 1, min_cols = 6;
+    if (pg) {      // read_pvar (Geno.cpp:887-939)
+      std::vector<std::string> t;
+      while (std::getline(f, line)) {
+        t = split_ws(line);
+        if (t.empty()) throw std::runtime_error("no blank lines should be before the header line in pvar file.");
+        if (t[0] == "#CHROM") break;
+      }
+      if (t.size() < 5) throw std::runtime_error("header of pvar file does not have correct format.");
+      for (const char* col : {"POS", "ID", "REF", "ALT"})
+        if (std::find(t.begin(), t.end(), col) == t.end()) throw std::runtime_error("header of pvar file does not have correct format.");
+      id_col = (size_t)(std::find(t.begin(), t.end(), "ID") - t.begin());
+      min_cols = 5;
+    }
+    int64_t lineno = 0;
+    while (std::getline(f, line)) {
+      auto t = split_ws(line);
+      if (t.size() < min_cols || id_col >= t.size()) throw std::runtime_error("incorrectly formatted " + kind + " file at line " + std::to_string(lineno + 1));
+      if (chr_str_to_int(t[0], p.nchrom) <= 0) throw std::runtime_error("unknown chromosome code in bgen file.");      // the reference's wording for every format (Geno.cpp:633, :932)
+      index[t[id_col]] = lineno++;
+    }
+    const std::string sfn = open_text(pre + (bed ? ".fam" : ".psam"));
+    TextIn fs(sfn);
+    if (!fs) throw std::runtime_error("cannot open file : " + sfn);
+    if (pg) {      // read_psam (Geno.cpp:1015-1046)
+      std::vector<std::string> t;
+      while (std::getline(fs, line)) {
+        t = split_ws(line);
+        if (t.empty()) throw std::runtime_error("no blank lines should be before the header line in psam file.");
+        if (t[0] == "#IID") throw std::runtime_error("invalid header (must start with #FID [not #IID]).");
+        if (t[0] == "#FID") break;
+      }
+      if (t.size() < 2 || t[1] != "IID") throw std::runtime_error("header does not have the correct format.");
+    }
+    while (std::getline(fs, line)) {
+      auto t = split_ws(line);
+      if (t.size() < (bed ? 6u : 2u)) throw std::runtime_error("incorrectly formatted " + std::string(bed ? "fam" : "psam") + " file at line " + std::to_string(fids.size() + 1));
+      fids.push_back(t[0] + "_" + t[1]);
+    }
+    if (pg) {      // prep_pgen (Geno.cpp:1105-1125)
+      if (rg_pgen_open(&pgh, (pre + ".pgen").c_str()) != RG_PGEN_OK) throw std::runtime_error(rg_pgen_last_error(pgh));
+      int64_t ns = 0, nv = 0;
+      rg_pgen_info(pgh, &ns, &nv, nullptr, nullptr, nullptr);
+      if (ns != (int64_t)fids.size()) throw std::runtime_error("number of samples in pgen file and psam file don't match.");
+      if (nv != (int64_t)index.size()) throw std::runtime_error("number of variants in pgen file and pvar file don't match.");
+    }
+  } else {      // setup_bgen (Geno.cpp:4289-4364)
+    sout << "      -extracting variants from file [" << pre << "]\n";
+    if (rg_bgen_open(&bgh, pre.c_str()) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(bgh));
+    int64_t ns = 0, nv = 0;
+    int32_t has_ids = 0;
+    rg_bgen_info(bgh, &ns, &nv, nullptr, &has_ids);
+    for (int64_t j = 0; j < nv; ++j) {
+      const char *chrom, *rsid;
+      rg_bgen_variant(bgh, j, &chrom, nullptr, &rsid, nullptr, nullptr, nullptr);
+      if (chr_str_to_int(chrom, p.nchrom) <= 0) throw std::runtime_error("unknown chromosome code in bgen file.");
+      index[rsid] = j;
+    }
+    if (!p.condition_sample.empty()) {      // read_bgen_sample (Geno.cpp:458-516)
+      TextIn f(p.condition_sample);
+      if (!f) throw std::runtime_error("cannot open file : " + p.condition_sample);
+      std::string line;
+      int nline = 0;
+      while (std::getline(f, line)) {
+        auto t = split_ws(line);
+        if (t.size() < 2) throw std::runtime_error("incorrectly formatted sample file at line" + std::to_string(fids.size() + 1));
+        if (nline == 0) { if (t[0] != "ID_1" || t[1] != "ID_2") throw std::runtime_error("header of the sample file must start with: ID_1 ID_2"); }
+        else if (nline == 1) { if (t[0] != "0" || t[1] != "0") throw std::runtime_error("second line of sample file must start with: 0 0."); }
+        else fids.push_back(t[0] + "_" + t[1]);
+        ++nline;
+      }
+      if ((int64_t)fids.size() != ns) throw std::runtime_error("number of samples in BGEN file does not match that in the sample file.");
+    } else {
+      if (!has_ids) throw std::runtime_error("bgen file has no sample identifiers; specify a sample file with --condition-file-sample");
+      for (int64_t i = 0; i < ns; ++i) { const char* id; rg_bgen_sample_id(bgh, i, &id); fids.push_back(id); }
+    }
+  }
+  // the file's samples that are samples of the run with covariate data
+  std::unordered_map<std::string, int64_t> idx;
+  idx.reserve((size_t)N * 2);
+  for (int64_t i = 0; i < N; ++i) idx[r.ids[i]] = i;
+  const int64_t nf = (int64_t)fids.size();
+  std::vector<int64_t> where((size_t)nf, -1);
+  int64_t nkeep = 0;
+  for (int64_t i = 0; i < nf; ++i) {
+    auto it = idx.find(fids[i]);
+    if (it != idx.end() && in_cov[it->second]) { where[i] = it->second; ++nkeep; }
+  }
+  if (nkeep == 0) throw std::runtime_error("none of the analyzed samples are present in the file");
+  // get_snps_offset (Geno.cpp:4201-4215) and the checks of extract_from_genofile (:4254-4258)
+  const size_t nstart = r.cond_snps.size();
+  for (auto it = r.cond_snps.begin(); it != r.cond_snps.end();) {
+    auto f = index.find(it->first);
+    if (f == index.end()) it = r.cond_snps.erase(it);
+    else { it->second = f->second; ++it; }
+  }
+  if (r.cond_snps.empty()) throw std::runtime_error("none of the conditional variants were found in the genotype file");
+  if (r.cond_snps.size() != nstart) throw std::runtime_error(std::to_string(nstart - r.cond_snps.size()) + " of the variants could not be found in the genotype file");
+  sout << "      -n_used = " << r.cond_snps.size() << std::endl;
+  cols.assign((size_t)N * r.cond_snps.size(), -3.0);
+  std::vector<double> full((size_t)nf);
+  std::vector<uint8_t> row;
+  int32_t has_dosage = 0;      // ginfo.dosage_mode: a .pgen with a dosage track is read with Read(), not ReadHardcalls() (Geno.cpp:4566-4569)
+  if (pg) rg_pgen_info(pgh, nullptr, nullptr, nullptr, nullptr, &has_dosage);
+  size_t c = 0;
+  for (auto& kv : r.cond_snps) {
+    if (bed) {
+      read_bed_row(pre + ".bed", kv.second, (nf + 3) / 4, row);
+      for (int64_t i = 0; i < nf; ++i) full[i] = bed_call(row.data(), i);
+    } else if (pg) {
+      if ((has_dosage ? rg_pgen_read_dosages(pgh, kv.second, full.data()) : rg_pgen_read_hardcalls(pgh, kv.second, full.data())) != RG_PGEN_OK)
+        throw std::runtime_error(rg_pgen_last_error(pgh));
+    } else {
+      if (rg_bgen_read_dosages(bgh, 1, &kv.second, 0, full.data(), nf) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(bgh));
+    }
+    double* col = cols.data() + c * (size_t)N;
+    for (int64_t i = 0; i < nf; ++i)
+      if (where[i] >= 0) col[where[i]] = full[i];
+    ++c;
+  }
+}
+
+// extract_condition_snps (Pheno.cpp:952-983), between covariate_read and the masks / the basis: one column per conditioning variant, in ascending
+// id order, appended to the raw covariates -- the orthonormal basis, the masks and the null models then see a wider X and nothing else changes.
+// Missing calls are mean-imputed and drop no sample.  The mean runs over the samples with covariate data (read_snp is handed ind_in_cov_and_geno
+// as its mask: Geno.cpp:3988-3992), samples without it get 0.  The log's n_cov does not count these columns.
+void condition_variants(Run& r, const std::vector<uint8_t>& in_cov, std::vector<double>& Xraw, int& ncols) {
+  const Params& p = r.p;
+  const int64_t N = r.N;
+  // the library's basis holds RG_S2_MAX_COV columns, intercept included (rg_s2_create / rg_ld_create): said here, before any work on the GPU
+  if (ncols + (int)r.cond_snps.size() > RG_S2_MAX_COV)
+    throw std::runtime_error(std::to_string(ncols - 1) + " covariates and " + std::to_string(r.cond_snps.size()) + " conditioning variants, with the intercept, make " +
+                             std::to_string(ncols + (int)r.cond_snps.size()) + " columns: step 2 holds at most " + std::to_string(RG_S2_MAX_COV) + ".");
+  std::vector<double> cols;
+  if (!p.condition_fmt.empty()) {
+    sout << "    +conditioning on variants in [" << p.condition_list << "]\n";
+    read_condition_file(r, in_cov, cols);
+  } else {
+    sout << "    +conditioning on variants in [" << p.condition_list << "] n_used = " << r.cond_snps.size() << std::endl;
+    std::vector<double> g;
+    for (auto& kv : r.cond_snps) {
+      read_main_variant(r, kv.second, g);
+      cols.insert(cols.end(), g.begin(), g.end());
+    }
+  }
+  const int nc = (int)r.cond_snps.size();
+  for (int c = 0; c < nc; ++c) {
+    double* col = cols.data() + (size_t)c * N;
+    double total = 0.0;
+    int64_t ns = 0;
+    for (int64_t i = 0; i < N; ++i)
+      if (in_cov[i] && col[i] != -3) { total += col[i]; ++ns; }
+    // a variant of a --condition-file without a single call stays at -3 for every sample (Geno.cpp:4482, :4534, :4581, :4655); in the main file the
+    // mean of no call is 0 / 0, as in the reference
+    if (ns == 0 && !p.condition_fmt.empty()) { for (int64_t i = 0; i < N; ++i) col[i] = -3; continue; }
+    const double mu = total / (double)ns;
+    for (int64_t i = 0; i < N; ++i) col[i] = !in_cov[i] ? 0.0 : (col[i] == -3 ? mu : col[i]);
+  }
+  Xraw.insert(Xraw.end(), cols.begin(), cols.end());
+  ncols += nc;
+  r.n_cond = nc;
 }
 
 void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841, :1903-1935
@@ -703,6 +987,7 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
   } else {
     Xraw.assign((size_t)N, 1.0);
   }
+  if (!r.cond_snps.empty()) condition_variants(r, in_cov, Xraw, ncols);      // Pheno.cpp:84-85
   // masks (Pheno.cpp:101, :810-841)
   const bool strict = p.strict || (r.P == 1 && !p.t2e);
   r.ain.assign(N, 0);

@@ -1,4 +1,4 @@
-/* rg_ld.h -- C ABI of the Step-2 LD matrix of a region (`regenie --step 2 --compute-corr`, hard calls).
+/* rg_ld.h -- C ABI of the Step-2 LD matrix of a region (`regenie --step 2 --compute-corr`, hard calls or dosages).
  *
  * What it replaces in the reference: Data::print_ld (Data.cpp:4368-4449) and the sparse matrix get_G_svs fills for it
  * (Data.cpp:4227-4304): for M variants and n analysed samples
@@ -15,6 +15,11 @@
  *
  * Layout: rows are 2-bit hard calls in .bed coding, sample-fastest, 4 per byte, low bits first (00 -> 2, 01 -> missing, 10 -> 1,
  * 11 -> 0 copies of the counted allele), as rg_s2_qt_block_packed takes them; flip != 0 counts the other allele.
+ * Dosages (the reference's Data::compute_ld_dosages, Data.cpp:3887-3980): rows of integers in units of 1 / scale (rg_ld_append_int).
+ * The same decomposition with g0 the integer dosage; A, B, D are exact: each row is split once into balanced base-128 int8 digit
+ * planes and a missing plane, A = sum_{p,q} 128^(p+q) P_p P_q^T on the i8 matrix cores, the int32 accumulators flushed into int64
+ * sums every 131,072 samples (a digit product reaches 4,096 and three plane pairs share an accumulator), so every n < 2^29 is exact.
+ * The fp64 epilogue divides A by scale^2 and B by scale; 8 M^2 bytes per integer sum instead of 4.
  * Conventions: 0 on success, < 0 on error with rg_ld_last_error(ctx); the library never falls back to the CPU.
  */
 #ifndef RG_LD_H
@@ -55,6 +60,16 @@ int rg_ld_force_columns(rg_ld_ctx* ctx, int32_t k, const int32_t* cols);
  * (host, [bs]) of the matrix.  A column can be given once. */
 int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, const int32_t* cols);
 
+/* A panel of bs variants as integer dosages: G [bs][ld >= n] uint16 in units of 1 / scale, 0xFFFF = missing, every other value
+ * <= 2 * scale, 1 <= scale <= 16384 (8-bit .bgen probabilities: scale 255; .pgen dosages: scale 16384); host pointer, or device when
+ * g_on_device.  A matrix holds either 2-bit panels or integer-dosage panels of one scale: anything else is RG_LD_ERR_ARG.  On append
+ * a row is split into balanced base-128 int8 digit planes (two when 2 * scale <= 8127, else three) and a 0/1 missing plane, which
+ * stay in device memory: M * 64 * ceil(n / 64) * (planes + 1) bytes, allocated by the first call; a matrix that does not fit the
+ * device is RG_LD_ERR_ARG (the bound covers the planes alone: the transient buffers of an append and the 8 M^2-byte sums and result of
+ * rg_ld_finish come on top, and running out of memory there is RG_LD_ERR_HIP).  A first call that fails after the allocation keeps
+ * it; a later call at a scale with another plane count replaces it. */
+int rg_ld_append_int(rg_ld_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int32_t scale, const int32_t* cols);
+
 /* The result in one of the three forms; out is a host pointer, or a device pointer when out_on_device (the quantisation runs on the
  * device either way: M (M - 1) bytes leave it, not 8 M^2).  tol: a diagonal entry in (-tol, 0) zeroes its row and column
  * (params.tol = 1e-8); numtol: a non-positive diagonal entry becomes numtol (params.numtol = 1e-6) -- Data.cpp:4386-4397.
@@ -65,6 +80,9 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
  * appended (no basis needed): A[i][j] = sum g0_i g0_j, B[i][j] = sum g0_i miss_j, Bt[i][j] = sum miss_i g0_j, D[i][j] = sum miss_i miss_j,
  * each int32 [na][nb] on the host; a NULL pointer skips that sum. */
 int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int32_t* A, int32_t* B, int32_t* Bt, int32_t* D);
+
+/* The same for integer-dosage panels, g0 in integer units (A in units of 1 / scale^2, B and Bt of 1 / scale): int64 [na][nb]. */
+int rg_ld_pair_sums_int(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int64_t* A, int64_t* B, int64_t* Bt, int64_t* D);
 
 /* Device time of the panel-pair Gram kernel of the last rg_ld_finish / rg_ld_pair_sums, in ms, and the tiles it computed. */
 double rg_ld_last_kernel_ms(const rg_ld_ctx* ctx);

@@ -171,17 +171,213 @@ __global__ __launch_bounds__(256) void k_ld_store(uint8_t* __restrict__ rows, in
   }
 }
 
-// LD[ci][cj] for the row pair (i, j), i <= j, written to both triangles of the M x M matrix.
-__global__ __launch_bounds__(256) void k_ld_combine(const int32_t* __restrict__ SA, const int32_t* __restrict__ SB, const int32_t* __restrict__ SD,
-                                                    int R, const double* __restrict__ mean, const double* __restrict__ gx, int C,
+// ---- integer dosages (rg_ld_append_int) ---------------------------------------------------------------------------------------------
+// The store: int8 planes [NP + 1][M][Kp], Kp = n rounded up to the K-step of 64: the NP balanced base-128 digits of a row
+// (g0 = sum_p 128^p d_p, d_p in [-64, 63]; the split of k_s2_int_rows, step2_qt.hip) and its missing indicator as plane NP, zero
+// past sample n.  The split is done once per row on append, not per K-step in the Gram kernel: profiles/ld_corr.md found k_ld_gram
+// held back by expanding its operands on the vector units at every K-step, and here a row is read by every tile pair of its panel.
+// bad: set when a value other than 0xFFFF exceeds vmax.  One workgroup per row.
+__global__ __launch_bounds__(256) void k_ld_store_int(const uint16_t* __restrict__ G, int64_t ldg, int64_t n, int64_t Kp, int NP, unsigned vmax,
+                                                      int8_t* __restrict__ planes, int64_t plane_stride, int32_t* __restrict__ bad) {
+  const uint16_t* g = G + (int64_t)blockIdx.x * ldg;
+  int8_t* out = planes + (int64_t)blockIdx.x * Kp;
+  bool over = false;
+  for (int64_t i0 = (int64_t)threadIdx.x * 4; i0 < Kp; i0 += 256 * 4) {
+    unsigned dig[3] = {0u, 0u, 0u}, mb = 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned raw = i0 + e < n ? g[i0 + e] : 0u;
+      const bool miss = raw == 0xFFFFu;
+      over |= !miss && raw > vmax;
+      int v = (miss || raw > vmax) ? 0 : (int)raw;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int d = ((v & 127) ^ 64) - 64;
+        dig[k] |= (unsigned)(uint8_t)(int8_t)d << (8 * e);
+        v = (v - d) >> 7;
+      }
+      mb |= (miss ? 1u : 0u) << (8 * e);
+    }
+    for (int k = 0; k < NP; ++k) *reinterpret_cast<unsigned*>(out + (int64_t)k * plane_stride + i0) = dig[k];
+    *reinterpret_cast<unsigned*>(out + (int64_t)NP * plane_stride + i0) = mb;
+  }
+  if (over) atomicOr(bad, 1);
+}
+
+// A digit product is at most 64 * 64 and at most three plane pairs share an accumulator (those of equal weight p + q), so an int32
+// accumulator is safe for floor((2^31 - 1) / (3 * 4096)) = 174,762 samples: it is flushed into the 64-bit sum every 2,048 K-steps
+// (131,072 samples).
+#define LDI_FLUSH 2048
+
+// One 128 x 128 tile of 64-bit sums: C[r][c] = sum_k (sum_p 128^p A_p[r][k]) (sum_q 128^q B_q[c][k]) for NA planes of the row
+// operand and NB of the column operand (a plane is ps bytes after the one before; rows are Kp bytes apart, Kp a multiple of 64).
+// A K-step's planes are staged in LDS once and every plane pair runs against that image; the pairs of equal weight p + q share an
+// accumulator.  512 threads: wave w owns rows [32 (w >> 1), +32) x columns [64 (w & 1), +64), so NA + NB - 1 accumulators are
+// 32 (NA + NB - 1) registers and two waves fit a SIMD (a 64 x 64 wave tile would need 320 accumulator registers for three digits).
+template <int NA, int NB>
+__device__ __forceinline__ void ldi_tile(const int8_t* __restrict__ A, int a_rows, const int8_t* __restrict__ B, int b_rows, bool same, int64_t Kp,
+                                         int64_t ps, long long* __restrict__ C, int64_t ldc, uint8_t* smem) {
+  constexpr int NW = NA + NB - 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  v16i acc[NW][2];
+#pragma unroll
+  for (int w = 0; w < NW; ++w)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[w][j][r] = 0;
+
+  // staging: thread -> (operand, row, half of the 64-byte K-step)
+  const bool isA = tid < 2 * LT;
+  const int srow = (tid & (2 * LT - 1)) >> 1, half = tid & 1;
+  constexpr int NS = NA > NB ? NA : NB;
+  const int my_np = isA ? NA : NB;
+  const bool do_stage = isA || !same;
+  const bool valid = do_stage && (isA ? srow < a_rows : srow < b_rows);
+  const int8_t* gbase = (isA ? A : B) + (int64_t)srow * Kp + half * 32;
+  const int b_off = same ? 0 : NA * LT * LPITCH;
+  const int my_off = (isA ? 0 : NA * LT * LPITCH) + srow * LPITCH + half * 32;
+  const int64_t nk = Kp / 64;
+  uint4 w0[NS], w1[NS];
+#pragma unroll
+  for (int p = 0; p < NS; ++p) {
+    w0[p] = make_uint4(0u, 0u, 0u, 0u);
+    w1[p] = w0[p];
+    if (valid && p < my_np) {
+      w0[p] = *reinterpret_cast<const uint4*>(gbase + (int64_t)p * ps);
+      w1[p] = *reinterpret_cast<const uint4*>(gbase + (int64_t)p * ps + 16);
+    }
+  }
+  bool first = true;
+  for (int64_t k = 0; k < nk; ++k) {
+    if (k) __syncthreads();   // the image of the previous step has been read
+    if (do_stage) {
+#pragma unroll
+      for (int p = 0; p < NS; ++p)
+        if (p < my_np) {
+          *reinterpret_cast<uint4*>(smem + my_off + p * LT * LPITCH) = w0[p];
+          *reinterpret_cast<uint4*>(smem + my_off + p * LT * LPITCH + 16) = w1[p];
+        }
+    }
+    if (valid && k + 1 < nk) {   // in flight while this step is multiplied
+#pragma unroll
+      for (int p = 0; p < NS; ++p)
+        if (p < my_np) {
+          w0[p] = *reinterpret_cast<const uint4*>(gbase + (int64_t)p * ps + (k + 1) * 64);
+          w1[p] = *reinterpret_cast<const uint4*>(gbase + (int64_t)p * ps + (k + 1) * 64 + 16);
+        }
+    }
+    __syncthreads();
+    const uint8_t* sA = smem;
+    const uint8_t* sB = smem + b_off;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int koff = ks * 32 + (lane >> 5) * 16;
+      v4i af[NA], bf[NB][2];
+#pragma unroll
+      for (int p = 0; p < NA; ++p) af[p] = *reinterpret_cast<const v4i*>(sA + (p * LT + wr * 32 + (lane & 31)) * LPITCH + koff);
+#pragma unroll
+      for (int q = 0; q < NB; ++q)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bf[q][j] = *reinterpret_cast<const v4i*>(sB + (q * LT + wc * 64 + j * 32 + (lane & 31)) * LPITCH + koff);
+#pragma unroll
+      for (int p = 0; p < NA; ++p)
+#pragma unroll
+        for (int q = 0; q < NB; ++q)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[p + q][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[p], bf[q][j], acc[p + q][j], 0, 0, 0);
+    }
+    if (((k + 1) % LDI_FLUSH) == 0 || k + 1 == nk) {
+      // C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int col = wc * 64 + j * 32 + (lane & 31);
+          long long v = 0;
+#pragma unroll
+          for (int w = NW - 1; w >= 0; --w) { v = v * 128 + (long long)acc[w][j][r]; acc[w][j][r] = 0; }
+          if (row < a_rows && col < b_rows) {
+            long long* c = C + (int64_t)row * ldc + col;
+            *c = first ? v : *c + v;   // the tile is this workgroup's alone
+          }
+        }
+      first = false;
+    }
+  }
+}
+
+// k_ld_gram for the plane store: the same grid, tile-pair order and meaning of tri, kinds, tile_miss and the four sums (64-bit
+// here); row r of the matrix is row r of every plane.
+template <int NP>
+__global__ __launch_bounds__(512) void k_ld_gram_int(const int8_t* __restrict__ planes, int64_t Kp, int64_t ps, int a0, int na, int b0, int nb, int tri,
+                                                     int kinds, const uint8_t* __restrict__ tile_miss, long long* SA, long long* SB, long long* SBt,
+                                                     long long* SD, int64_t ldc) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * NP * LT * LPITCH];
+  const int nta = (na + LT - 1) / LT, ntb = (nb + LT - 1) / LT;
+  int tidx = blockIdx.x;
+  {  // XCD-aware remap, as k_ld_gram
+    const int nwg = gridDim.x;
+    const int q = nwg / 8, r = nwg % 8, xcd = tidx % 8, k = tidx / 8;
+    tidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  }
+  int tr, tc;
+  if (tri) {
+    tc = (int)((sqrtf(8.0f * tidx + 1.0f) - 1.0f) * 0.5f);
+    while ((tc + 1) * (tc + 2) / 2 <= tidx) ++tc;
+    while (tc * (tc + 1) / 2 > tidx) --tc;
+    tr = tidx - tc * (tc + 1) / 2;
+  } else {
+    tr = tidx / ntb;
+    tc = tidx - tr * ntb;
+  }
+  if (tr >= nta || tc >= ntb) return;
+  const int kind = blockIdx.y;
+  if (!((kinds >> kind) & 1)) return;
+  const int8_t* Ar = planes + (int64_t)(a0 + tr * LT) * Kp;
+  const int8_t* Bc = planes + (int64_t)(b0 + tc * LT) * Kp;
+  const int8_t* Am = Ar + NP * ps;
+  const int8_t* Bm = Bc + NP * ps;
+  const int ar = min(LT, na - tr * LT), bc = min(LT, nb - tc * LT);
+  const bool diag = tri && tr == tc;
+  if (kind == 0) {
+    ldi_tile<NP, NP>(Ar, ar, Bc, bc, diag, Kp, ps, SA + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  } else if (kind == 1) {
+    if (tile_miss && !tile_miss[tc]) return;
+    ldi_tile<NP, 1>(Ar, ar, Bm, bc, false, Kp, ps, SB + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  } else if (kind == 2) {
+    if (tri) {
+      if (diag || (tile_miss && !tile_miss[tr])) return;
+      ldi_tile<NP, 1>(Bc, bc, Am, ar, false, Kp, ps, SB + (int64_t)tc * LT * ldc + (int64_t)tr * LT, ldc, smem);
+    } else {
+      ldi_tile<1, NP>(Am, ar, Bc, bc, false, Kp, ps, SBt + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+    }
+  } else {
+    if (tile_miss && !(tile_miss[tr] && tile_miss[tc])) return;
+    ldi_tile<1, 1>(Am, ar, Bm, bc, diag, Kp, ps, SD + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+  }
+}
+
+
+// LD[ci][cj] for the row pair (i, j), i <= j, written to both triangles of the M x M matrix.  T = int32_t: hard calls (scale 1, no
+// division); T = long long: integer dosages, A / scale^2 and B / scale in genotype units (means are in genotype units already).
+template <class T>
+__global__ __launch_bounds__(256) void k_ld_combine(const T* __restrict__ SA, const T* __restrict__ SB, const T* __restrict__ SD, int R, double scale,
+                                                    const double* __restrict__ mean, const double* __restrict__ gx, int C,
                                                     const int32_t* __restrict__ col, double* __restrict__ LD, int M) {
+  constexpr bool kInt = sizeof(T) == 8;
   const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (i >= R || j >= R || i > j) return;
   double v = (double)SA[(int64_t)i * R + j];
+  if (kInt) v = __ddiv_rn(v, __dmul_rn(scale, scale));
   if (SB) {
     const double mi = mean[i], mj = mean[j];
-    v = __dadd_rn(v, __dmul_rn(mj, (double)SB[(int64_t)i * R + j]));
-    v = __dadd_rn(v, __dmul_rn(mi, (double)SB[(int64_t)j * R + i]));
+    double bij = (double)SB[(int64_t)i * R + j], bji = (double)SB[(int64_t)j * R + i];
+    if (kInt) { bij = __ddiv_rn(bij, scale); bji = __ddiv_rn(bji, scale); }
+    v = __dadd_rn(v, __dmul_rn(mj, bij));
+    v = __dadd_rn(v, __dmul_rn(mi, bji));
     v = __dadd_rn(v, __dmul_rn(__dmul_rn(mi, mj), (double)SD[(int64_t)i * R + j]));
   }
   double p = 0.0;
@@ -241,6 +437,11 @@ struct rg_ld_ctx {
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   uint8_t* rows = nullptr;            // [M][ld] in the order appended
+  int kind = 0;                       // 0: no panel yet, 1: 2-bit hard calls (rows), 2: integer dosages (planes)
+  int scale = 0, np = 0;              // integer dosages: units of 1 / scale, np digit planes
+  int64_t kp = 0;                     // n rounded up to 64
+  int8_t* planes = nullptr;           // [planes_np + 1][M][kp], allocated by the first rg_ld_append_int
+  int planes_np = 0;                  // the plane count the store was sized for (np once a panel is held)
   rg_s2_ctx* s2 = nullptr;            // the contraction primitive (X^T g), created by rg_ld_set_basis
   std::vector<int32_t> col_of_row;    // [nrows]
   std::vector<uint8_t> col_state;     // [M] 0: open, 1: appended, 2: forced
@@ -284,6 +485,7 @@ int rg_ld_create(rg_ld_ctx** out, int device, int64_t n, int32_t n_cov, int32_t 
   if (device < 0 || device >= ndev) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_create: device index out of range");
   ctx->dev = device; ctx->n = n; ctx->C = n_cov; ctx->M = n_col;
   ctx->ld = (n + 63) / 64 * 16;
+  ctx->kp = (n + 63) / 64 * 64;
   LD_HIP(hipSetDevice(device));
   LD_HIP(hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking));
   LD_HIP(hipEventCreate(&ctx->e0));
@@ -300,6 +502,7 @@ void rg_ld_destroy(rg_ld_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->st);
     if (ctx->s2) rg_s2_destroy(ctx->s2);
     if (ctx->rows) (void)hipFree(ctx->rows);
+    if (ctx->planes) (void)hipFree(ctx->planes);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
     if (ctx->e1) (void)hipEventDestroy(ctx->e1);
     (void)hipStreamDestroy(ctx->st);
@@ -343,6 +546,7 @@ int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, in
   if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: context was not created");
   const int64_t n = ctx->n, nbytes = (n + 3) / 4;
   if (!rows || !cols || bs < 1 || ld < nbytes) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: bad arguments (need bs >= 1, ld >= ceil(n / 4))");
+  if (ctx->kind == 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: the matrix holds integer-dosage panels (rg_ld_append_int); the two kinds cannot be mixed");
   if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
   {
     std::vector<uint8_t> seen(ctx->col_state);
@@ -379,6 +583,115 @@ int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, in
   }
   for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
   ctx->nrows += bs;
+  ctx->kind = 1;
+  return RG_LD_OK;
+}
+
+int rg_ld_append_int(rg_ld_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int32_t scale, const int32_t* cols) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: context was not created");
+  const int64_t n = ctx->n;
+  if (!G || !cols || bs < 1 || ld < n) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: bad arguments (need bs >= 1, ld >= n)");
+  if (scale < 1 || scale > 16384) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: need 1 <= scale <= 16384");
+  if (ctx->kind == 1) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the matrix holds 2-bit panels (rg_ld_append); the two kinds cannot be mixed");
+  if (ctx->kind == 2 && scale != ctx->scale)
+    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the matrix holds panels of scale " + std::to_string(ctx->scale) + "; one matrix has one scale");
+  if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
+  {
+    std::vector<uint8_t> seen(ctx->col_state);
+    for (int j = 0; j < bs; ++j) {
+      if (cols[j] < 0 || cols[j] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: column index out of range");
+      if (seen[cols[j]]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: column " + std::to_string(cols[j]) + " is used twice");
+      seen[cols[j]] = 1;
+    }
+  }
+  LD_HIP(hipSetDevice(ctx->dev));
+  const int np = 2 * scale <= 8127 ? 2 : 3;      // the rule of rg_s2_qt_block_int: two balanced base-128 digits reach 63 + 63 * 128
+  const int64_t kp = ctx->kp, ps = (int64_t)ctx->M * kp;
+  if (ctx->planes && ctx->planes_np != np) {      // left by a first append that failed at a scale with another plane count
+    LD_HIP(hipFree(ctx->planes));
+    ctx->planes = nullptr;
+  }
+  if (!ctx->planes) {      // M * kp * (np + 1) bytes; a matrix that does not fit is an error, there is no second route
+    const size_t need = (size_t)ps * (np + 1);
+    size_t free_b = 0, total_b = 0;
+    LD_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+      return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the digit planes of the matrix need " + std::to_string(need) + " bytes (M * n * " + std::to_string(np + 1) +
+                                             "), the device has " + std::to_string(free_b) + " free");
+    LD_HIP(hipMalloc((void**)&ctx->planes, need));
+    ctx->planes_np = np;
+  }
+  DevBuf dG, dBad;
+  const uint16_t* src = G;
+  int64_t lds = ld;
+  if (!g_on_device) {
+    lds = (n + 7) / 8 * 8;
+    LD_HIP(dG.alloc((size_t)bs * lds * sizeof(uint16_t)));
+    LD_HIP(hipMemcpy2DAsync(dG.p, lds * sizeof(uint16_t), G, ld * sizeof(uint16_t), n * sizeof(uint16_t), bs, hipMemcpyHostToDevice, ctx->st));
+    src = dG.as<uint16_t>();
+  }
+  LD_HIP(dBad.alloc(sizeof(int32_t)));
+  LD_HIP(hipMemsetAsync(dBad.p, 0, sizeof(int32_t), ctx->st));
+  hipLaunchKernelGGL(k_ld_store_int, dim3(bs), dim3(256), 0, ctx->st, src, lds, n, kp, np, (unsigned)(2 * scale), ctx->planes + (int64_t)ctx->nrows * kp, ps,
+                     dBad.as<int32_t>());
+  LD_HIP(hipGetLastError());
+  int32_t bad = 0;
+  LD_HIP(hipMemcpyAsync(&bad, dBad.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  if (bad) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: a dosage is above 2 * scale = " + std::to_string(2 * scale) + " (0xFFFF is the missing value)");
+  const int r0 = ctx->nrows, C = ctx->C;
+  ctx->mean.resize((size_t)r0 + bs, 0.0);
+  ctx->nmiss.resize((size_t)r0 + bs, 0);
+  ctx->gx.resize(((size_t)r0 + bs) * C, 0.0);
+  if (ctx->s2) {  // X^T g0 and X^T miss in genotype units, the sum and the number of the observed entries
+    std::vector<double> sums((size_t)bs * 2 * C), vstat((size_t)bs * 4);
+    rg_s2_contract_out co = {sums.data(), nullptr, nullptr, vstat.data()};
+    if (rg_s2_contract_int(ctx->s2, src, lds, bs, 1, scale, &co) != RG_S2_OK)
+      return ld_fail(ctx, RG_LD_ERR_HIP, std::string("rg_ld_append_int: ") + rg_s2_last_error(ctx->s2));
+    for (int j = 0; j < bs; ++j) {
+      const double* v4 = vstat.data() + (size_t)j * 4;
+      const double m = v4[2] > 0 ? v4[0] / (double)scale / v4[2] : 0.0;
+      ctx->mean[r0 + j] = m;
+      ctx->nmiss[r0 + j] = (int32_t)(n - (int64_t)v4[2]);
+      for (int c = 0; c < C; ++c) ctx->gx[(size_t)(r0 + j) * C + c] = sums[((size_t)j * 2) * C + c] + m * sums[((size_t)j * 2 + 1) * C + c];
+    }
+  }
+  for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
+  ctx->nrows += bs;
+  ctx->kind = 2; ctx->scale = scale; ctx->np = np;
+  return RG_LD_OK;
+}
+
+int rg_ld_pair_sums_int(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int64_t* A, int64_t* B, int64_t* Bt, int64_t* D) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: context was not created");
+  if (ctx->kind != 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: the matrix holds no integer-dosage panel");
+  if (a0 < 0 || b0 < 0 || na < 1 || nb < 1 || (int64_t)a0 + na > ctx->nrows || (int64_t)b0 + nb > ctx->nrows)
+    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: row range outside the panels appended");
+  LD_HIP(hipSetDevice(ctx->dev));
+  const size_t cnt = (size_t)na * nb;
+  DevBuf S;
+  LD_HIP(S.alloc(4 * cnt * sizeof(long long)));
+  long long* s = S.as<long long>();
+  const int nt = ((na + LT - 1) / LT) * ((nb + LT - 1) / LT);
+  const int kinds = (A ? 1 : 0) | (B ? 2 : 0) | (Bt ? 4 : 0) | (D ? 8 : 0);
+  const int64_t ps = (int64_t)ctx->M * ctx->kp;
+  LD_HIP(hipEventRecord(ctx->e0, ctx->st));
+  if (ctx->np == 2)
+    hipLaunchKernelGGL(k_ld_gram_int<2>, dim3(nt, 4), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s,
+                       s + cnt, s + 2 * cnt, s + 3 * cnt, (int64_t)nb);
+  else
+    hipLaunchKernelGGL(k_ld_gram_int<3>, dim3(nt, 4), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s,
+                       s + cnt, s + 2 * cnt, s + 3 * cnt, (int64_t)nb);
+  LD_HIP(hipGetLastError());
+  LD_HIP(hipEventRecord(ctx->e1, ctx->st));
+  int64_t* outs[4] = {A, B, Bt, D};
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) LD_HIP(hipMemcpyAsync(outs[k], s + k * cnt, cnt * sizeof(long long), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  float ms = 0.f;
+  LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+  ctx->last_ms = ms;
+  ctx->last_tiles = (int64_t)nt * __builtin_popcount(kinds);
   return RG_LD_OK;
 }
 
@@ -386,6 +699,7 @@ int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t 
   if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: context was not created");
   if (a0 < 0 || b0 < 0 || na < 1 || nb < 1 || (int64_t)a0 + na > ctx->nrows || (int64_t)b0 + nb > ctx->nrows)
     return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: row range outside the panels appended");
+  if (ctx->kind == 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: the matrix holds integer-dosage panels (rg_ld_pair_sums_int)");
   LD_HIP(hipSetDevice(ctx->dev));
   const size_t cnt = (size_t)na * nb;
   DevBuf S;
@@ -428,13 +742,15 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
   LD_HIP(hipMemsetAsync(dLD.p, 0, MM * sizeof(double), ctx->st));
   ctx->last_ms = 0.0;
   ctx->last_tiles = 0;
+  const bool ints = ctx->kind == 2;
+  const size_t ssz = ints ? sizeof(long long) : sizeof(int32_t);
   if (R > 0) {
-    LD_HIP(dSA.alloc(RR * sizeof(int32_t)));
+    LD_HIP(dSA.alloc(RR * ssz));
     if (any_miss) {
-      LD_HIP(dSB.alloc(RR * sizeof(int32_t)));
-      LD_HIP(dSD.alloc(RR * sizeof(int32_t)));
-      LD_HIP(hipMemsetAsync(dSB.p, 0, RR * sizeof(int32_t), ctx->st));
-      LD_HIP(hipMemsetAsync(dSD.p, 0, RR * sizeof(int32_t), ctx->st));
+      LD_HIP(dSB.alloc(RR * ssz));
+      LD_HIP(dSD.alloc(RR * ssz));
+      LD_HIP(hipMemsetAsync(dSB.p, 0, RR * ssz, ctx->st));
+      LD_HIP(hipMemsetAsync(dSD.p, 0, RR * ssz, ctx->st));
     }
     LD_HIP(dTm.alloc(tile_miss.size()));
     LD_HIP(dMean.alloc(sizeof(double) * R));
@@ -446,8 +762,16 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
     LD_HIP(hipMemcpyAsync(dCol.p, ctx->col_of_row.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->st));
     const int npair = nt * (nt + 1) / 2;
     LD_HIP(hipEventRecord(ctx->e0, ctx->st));
-    hipLaunchKernelGGL(k_ld_gram, dim3(npair, any_miss ? 4 : 1), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, 0, R, 0, R, 1, 0xF, dTm.as<uint8_t>(), dSA.as<int32_t>(),
-                       dSB.as<int32_t>(), (int32_t*)nullptr, dSD.as<int32_t>(), (int64_t)R);
+    const int64_t ps = (int64_t)M * ctx->kp;
+    if (!ints)
+      hipLaunchKernelGGL(k_ld_gram, dim3(npair, any_miss ? 4 : 1), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, 0, R, 0, R, 1, 0xF, dTm.as<uint8_t>(), dSA.as<int32_t>(),
+                         dSB.as<int32_t>(), (int32_t*)nullptr, dSD.as<int32_t>(), (int64_t)R);
+    else if (ctx->np == 2)
+      hipLaunchKernelGGL(k_ld_gram_int<2>, dim3(npair, any_miss ? 4 : 1), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, 0, R, 0, R, 1, 0xF,
+                         (const uint8_t*)dTm.as<uint8_t>(), dSA.as<long long>(), dSB.as<long long>(), (long long*)nullptr, dSD.as<long long>(), (int64_t)R);
+    else
+      hipLaunchKernelGGL(k_ld_gram_int<3>, dim3(npair, any_miss ? 4 : 1), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, 0, R, 0, R, 1, 0xF,
+                         (const uint8_t*)dTm.as<uint8_t>(), dSA.as<long long>(), dSB.as<long long>(), (long long*)nullptr, dSD.as<long long>(), (int64_t)R);
     LD_HIP(hipGetLastError());
     LD_HIP(hipEventRecord(ctx->e1, ctx->st));
     int64_t tiles = npair;
@@ -456,8 +780,14 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
         for (int b = a; b < nt; ++b) tiles += (tile_miss[b] ? 1 : 0) + ((a != b && tile_miss[a]) ? 1 : 0) + ((tile_miss[a] && tile_miss[b]) ? 1 : 0);
     ctx->last_tiles = tiles;
     const dim3 g2((R + 15) / 16, (R + 15) / 16);
-    hipLaunchKernelGGL(k_ld_combine, g2, dim3(256), 0, ctx->st, dSA.as<int32_t>(), any_miss ? dSB.as<int32_t>() : (const int32_t*)nullptr, dSD.as<int32_t>(), R,
-                       dMean.as<double>(), dGx.as<double>(), C, dCol.as<int32_t>(), dLD.as<double>(), M);
+    if (!ints)
+      hipLaunchKernelGGL(k_ld_combine<int32_t>, g2, dim3(256), 0, ctx->st, (const int32_t*)dSA.as<int32_t>(), any_miss ? dSB.as<int32_t>() : (const int32_t*)nullptr,
+                         (const int32_t*)dSD.as<int32_t>(), R, 1.0, (const double*)dMean.as<double>(), (const double*)dGx.as<double>(), C,
+                         (const int32_t*)dCol.as<int32_t>(), dLD.as<double>(), M);
+    else
+      hipLaunchKernelGGL(k_ld_combine<long long>, g2, dim3(256), 0, ctx->st, (const long long*)dSA.as<long long>(),
+                         any_miss ? dSB.as<long long>() : (const long long*)nullptr, (const long long*)dSD.as<long long>(), R, (double)ctx->scale,
+                         (const double*)dMean.as<double>(), (const double*)dGx.as<double>(), C, (const int32_t*)dCol.as<int32_t>(), dLD.as<double>(), M);
     LD_HIP(hipGetLastError());
   }
   const dim3 gM((M + 15) / 16, (M + 15) / 16);

@@ -115,6 +115,7 @@ struct Params {
   double range_min = 0, range_max = 0;
   // --step 2 --compute-corr: the LD matrix of a region (Data::ld_comp, Data.cpp:3807-3848; driver_ld.cpp)
   bool compute_corr = false, corr_text = false, forcein_vars = false;
+  bool ld_dosages = false;   // --ld-dosages: the LD matrix of dosage input (--bgen, a .pgen dosage track), Data::compute_ld_dosages; refused without it
   // --step 2 --condition-list FILE [--condition-file FORMAT,FILE [--condition-file-sample FILE]] [--max-condition-vars N]: the listed variants become
   // covariates and leave the tested set (Regenie.cpp:217-219, :277, :516, :714-722; condition_variants in driver_inputs.cpp)
   std::string condition_list, condition_fmt, condition_file, condition_sample;

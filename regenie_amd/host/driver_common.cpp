@@ -356,6 +356,7 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
     else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
     else if (a == "--forcein-vars") p.forcein_vars = true;
+    else if (a == "--ld-dosages") p.ld_dosages = true;
     else if (a == "--ld-extract") { need(i); usage_error("--ld-extract (burden masks in the LD matrix) is not built: use --extract [--forcein-vars] for single variants."); }
     else if (a == "--skip-scaleG") usage_error("--skip-scaleG (the LD matrix of unscaled genotypes) is not built.");
     else if (a == "--sparse-thr") { need(i); usage_error("--sparse-thr (the sparsified LD matrix, which needs --skip-scaleG) is not built."); }
@@ -429,11 +430,13 @@ Params parse_args(int argc, char** argv) {
   if (p.compute_corr) {          // Regenie.cpp:522-535
     if (p.step != 2) usage_error("--compute-corr / --output-corr-text need --step 2.");
     if (!p.exclude.empty()) usage_error("cannot use --exclude with --compute-corr (use --extract instead)");
-    if (!p.bgen.empty()) usage_error("--compute-corr with dosage input (--bgen) is not built: the LD matrix is computed from hard calls (--bed, or a .pgen without a dosage track).");
+    if (!p.bgen.empty() && !p.ld_dosages)
+      usage_error("--compute-corr with dosage input (--bgen) is not built into the default mode, which computes the LD matrix from hard calls (--bed, or a .pgen without a dosage track): add --ld-dosages for the LD matrix of the dosages themselves.");
     if (p.gpus > 1) usage_error("--compute-corr on more than one GPU (--gpus) is not built.");
     if (p.forcein_vars && p.extract.size() > 1) usage_error("cannot have multiple extract files");      // Geno.cpp:1352
     p.forcein_vars = p.forcein_vars && !p.extract.empty();
   }
+  if (p.ld_dosages && !p.compute_corr) usage_error("--ld-dosages goes with --compute-corr / --output-corr-text.");
   if (p.step == 2 && !p.compute_corr) {
     if (p.pred_list.empty()) usage_error("option '--pred' is required (use the _pred.list file written by step 1).");
     if (p.firth && !p.bt) usage_error("option '--firth' applies to binary traits (--bt).");

@@ -2,7 +2,8 @@
 //
 // The host keeps what the reference's host does around print_ld: which variant takes which column (check_in_map_from_files /
 // check_ld_list, Geno.cpp:1343-1380, :1443-1453), the variant lists (write_snplist, Data.cpp:3862-3885), reading the 2-bit rows in
-// panels of --bsize, the two output formats.  Everything numeric -- the integer Gram of the panels, the covariate projection, the
+// panels of --bsize (or, for --bgen and .pgen dosages, the exact integer dosages as uint16 rows), the two output formats.
+// Everything numeric -- the integer Gram of the panels, the covariate projection, the
 // diagonal rules, the scaling and the 16-bit quantisation -- is the library's (include/rg_ld.h); there is no CPU path.
 #include "driver.h"
 
@@ -18,7 +19,10 @@ static void fmt_sig6(double v, std::string& out) {
 
 static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
   const Params& p = r.p;
-  if (r.dosage_mode) throw std::runtime_error("--compute-corr with dosage input (a .pgen with a dosage track) is not built: the LD matrix is computed from hard calls.");
+  if (r.dosage_mode && !p.ld_dosages)
+    throw std::runtime_error("--compute-corr with dosage input (a .pgen with a dosage track) is not built into the default mode, which computes the LD matrix from hard calls: add --ld-dosages for the LD matrix of the dosages themselves.");
+  if (p.ld_dosages && !r.dosage_mode) throw std::runtime_error("--ld-dosages needs dosage input (--bgen, or a .pgen with a dosage track).");
+  const bool dos = r.dosage_mode;      // --bgen, or a .pgen with a dosage track: Data::compute_ld_dosages (Data.cpp:3887-3980)
   {  // set_blocks_for_testing (Data.cpp:2155-2161)
     std::set<int> chrs(r.snp_chrom.begin(), r.snp_chrom.end());
     if (chrs.size() > 1) throw std::runtime_error("can only compute LD matrix for a single chromosome (use --chr/--chrList/--range).");
@@ -66,8 +70,9 @@ static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
 
   sout << std::left << std::setw(20) << " * block size" << ": [" << p.bsize << "]\n";
   const std::string out = p.out + ".corr";
-  if (p.corr_text) sout << " * computing correlation matrix in hard-call mode\n  + output to text file [" << out << "]\n";      // setup_output, Data.cpp:1986-2004
-  else sout << " * computing correlation matrix in hard-call mode (storing R^2 values)\n  + output to binary file [" << out << "]\n";
+  const char* runmode = dos ? "in dosage mode" : "in hard-call mode";
+  if (p.corr_text) sout << " * computing correlation matrix " << runmode << "\n  + output to text file [" << out << "]\n";      // setup_output, Data.cpp:1986-2004
+  else sout << " * computing correlation matrix " << runmode << " (storing R^2 values)\n  + output to binary file [" << out << "]\n";
   sout << "  + list of snps written to [" << out << ".snplist]\n  + n_snps = " << M << "\n\n";
 
   // analysed samples and the compact, sample-fastest covariate basis (as run_step2)
@@ -104,9 +109,12 @@ static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
 
   // get_G_svs (Data.cpp:4227-4304): the rows in panels of --bsize
   const int nchunks = (int)((present.size() + p.bsize - 1) / p.bsize);
-  sout << "** reading in single variant genotypes **\n  + " << present.size() << " variants in total split across " << nchunks << " blocks\n";
-  const int fd = r.pgen ? -1 : open((p.bed + ".bed").c_str(), O_RDONLY);
-  if (!r.pgen && fd < 0) throw std::runtime_error("cannot read bed file");
+  if (dos) {
+    sout << "** Computing LD matrix **\n";
+    if (nchunks > 0) sout << "  -> splitting across " << nchunks << " SV blocks\n";
+  } else sout << "** reading in single variant genotypes **\n  + " << present.size() << " variants in total split across " << nchunks << " blocks\n";
+  const int fd = (r.pgen || dos) ? -1 : open((p.bed + ".bed").c_str(), O_RDONLY);
+  if (!r.pgen && !dos && fd < 0) throw std::runtime_error("cannot read bed file");
   struct FdGuard { int fd; ~FdGuard() { if (fd >= 0) close(fd); } } fdg{fd};
   const int flip = (!r.pgen && p.ref_first) ? 1 : 0;      // .pgen rows always count ALT (as run_step2)
   int nthreads = p.threads > 0 ? p.threads : std::max(1, usable_cpus() - 1);
@@ -114,7 +122,107 @@ static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
   std::vector<uint8_t> rows, packed;
   std::vector<int64_t> vidx;
   std::vector<int32_t> cols;
-  for (int b = 0; b < nchunks; ++b) {
+  // get_G_svs(int, int) (Data.cpp:4049-4090) for dosages: the block as uint16 rows of exact integers -- 8-bit .bgen probabilities in
+  // units of 1 / 255 (the inflated blocks walked as the Step-2 read-ahead walks them), .pgen dosages in units of 1 / 16384 -- which the
+  // library splits into int8 digit planes.  A value that is no such integer is an error: there is no second route.
+  std::vector<uint16_t> g16;
+  std::vector<double> dbuf;
+  std::vector<uint8_t> raw;
+  int64_t block_bytes = 0;
+  // zlib files: the stored streams go to the device decoder (rg_bgen_dev_decode), whose uint16 rows are appended where they lie; a
+  // block with a variant the decoder turns down (status != 0), zstd and uncompressed files take the host route below
+  rg_bgen_dev* bdev = nullptr;
+  struct DevGuard { rg_bgen_dev*& d; ~DevGuard() { if (d && full_teardown()) rg_bgen_dev_destroy(d); } } devg{bdev};
+  std::vector<uint8_t> comp;
+  int64_t dev_blocks = 0, host_blocks = 0;
+  if (dos && r.bgenh) {
+    if (rg_bgen_block_bytes(r.bgenh, &block_bytes) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(r.bgenh));
+    block_bytes = (block_bytes + 63) / 64 * 64;
+    int32_t bcomp = 0;
+    rg_bgen_info(r.bgenh, nullptr, nullptr, &bcomp, nullptr);
+    if (bcomp == 1 && rg_bgen_dev_create(&bdev, p.device) == RG_BGEN_OK &&
+        rg_bgen_dev_set_samples(bdev, r.n_file, n, identity ? nullptr : file_idx.data(), 0, nullptr) != RG_BGEN_OK) {
+      rg_bgen_dev_destroy(bdev);
+      bdev = nullptr;
+    }
+  }
+  // false: the block is left to the host route
+  auto device_block = [&](int64_t j0, int bs) -> bool {
+    if (!bdev) return false;
+    int64_t need = 0;
+    if (rg_bgen_compressed_bytes(r.bgenh, bs, vidx.data(), &need) != RG_BGEN_OK) return false;
+    if ((int64_t)comp.size() < need) comp.resize((size_t)(need + need / 4));
+    std::vector<int64_t> off(bs);
+    std::vector<int32_t> clen(bs), ulen(bs), status(bs), maxq(bs);
+    if (rg_bgen_read_compressed(r.bgenh, bs, vidx.data(), comp.data(), (int64_t)comp.size(), off.data(), clen.data(), ulen.data(), std::min(nthreads, 32)) != RG_BGEN_OK)
+      return false;
+    rg_bgen_dev_out o;
+    memset(&o, 0, sizeof(o));
+    o.max_q = maxq.data(); o.status = status.data();
+    if (rg_bgen_dev_decode(bdev, 0, bs, comp.data(), off[bs - 1] + clen[bs - 1], off.data(), clen.data(), ulen.data(), p.ref_first ? 1 : 0, &o) != RG_BGEN_OK) return false;
+    for (int j = 0; j < bs; ++j) if (status[j] != 0) return false;
+    for (int j = 0; j < bs; ++j)
+      if (maxq[j] > 510)
+        throw std::runtime_error("variant '" + r.snp_ids[present[j0 + j]] + "' has a dosage that is not an integer in [0, 510] in units of 1/255 (probabilities that add up to more than 1): the LD matrix of such dosages is not built.");
+    if (!o.g16 || o.ld16 < n) return false;
+    ldcheck(rg_ld_append_int(ld, o.g16, o.ld16, bs, 1, 255, cols.data()));
+    return true;
+  };
+  for (int b = 0; dos && b < nchunks; ++b) {
+    const int64_t j0 = (int64_t)b * p.bsize;
+    const int bs = (int)std::min<int64_t>(p.bsize, (int64_t)present.size() - j0);
+    sout << "     - row " << b + 1 << "\n" << std::flush;
+    cols.resize(bs);
+    vidx.resize(bs);
+    for (int j = 0; j < bs; ++j) { vidx[j] = r.snp_offset[present[j0 + j]]; cols[j] = col_of_variant[present[j0 + j]]; }
+    if (r.bgenh && device_block(j0, bs)) { ++dev_blocks; continue; }
+    ++host_blocks;
+    g16.resize((size_t)bs * n);
+    std::vector<int> bad(bs, 0);
+    int scale = 255;
+    if (r.bgenh) {
+      raw.resize((size_t)bs * block_bytes);
+      if (rg_bgen_read_blocks(r.bgenh, bs, vidx.data(), raw.data(), block_bytes, std::min(nthreads, 32)) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(r.bgenh));
+      const bool rf = p.ref_first;
+      parallel_for(bs, nthreads, [&](int j) {
+        const uint8_t* blk = raw.data() + (size_t)j * block_bytes;
+        const uint8_t* ploidy = blk + 8;
+        const uint8_t* pr = blk + 10 + r.n_file;
+        uint16_t* q = g16.data() + (size_t)j * n;
+        for (int64_t k = 0; k < n; ++k) {
+          const int64_t i = file_idx[k];
+          if (ploidy[i] & 0x80) { q[k] = 0xFFFFu; continue; }
+          const unsigned b0 = pr[2 * i], b1 = pr[2 * i + 1];
+          // G * 255 = prob1 + 2 prob0, or with --ref-first prob1 + 2 max(1 - prob0 - prob1, 0) (Geno.cpp:2286-2290)
+          const unsigned qi = rf ? b1 + 2u * (b0 + b1 < 255u ? 255u - b0 - b1 : 0u) : b1 + 2u * b0;
+          if (qi > 510u) { bad[j] = 1; break; }      // prob0 + prob1 > 1 in the file: max_q > 510
+          q[k] = (uint16_t)qi;
+        }
+      });
+    } else {
+      scale = 16384;
+      dbuf.resize((size_t)bs * r.n_file);
+      if (rg_pgen_read_dosage_rows(r.pgen, bs, vidx.data(), dbuf.data(), r.n_file) != RG_PGEN_OK) throw std::runtime_error(rg_pgen_last_error(r.pgen));
+      parallel_for(bs, nthreads, [&](int j) {
+        const double* d = dbuf.data() + (size_t)j * r.n_file;
+        uint16_t* q = g16.data() + (size_t)j * n;
+        for (int64_t k = 0; k < n; ++k) {
+          const double g = d[file_idx[k]];
+          if (g == -3.0) { q[k] = 0xFFFFu; continue; }
+          const double v = g * 16384.0, rv = std::nearbyint(v);
+          if (std::fabs(v - rv) > 1e-6 || rv < 0 || rv > 2.0 * 16384.0) { bad[j] = 1; break; }
+          q[k] = (uint16_t)rv;
+        }
+      });
+    }
+    for (int j = 0; j < bs; ++j)
+      if (bad[j])
+        throw std::runtime_error("variant '" + r.snp_ids[present[j0 + j]] + "' has a dosage that is not an integer in [0, " + std::to_string(2 * scale) + "] in units of 1/" +
+                                 std::to_string(scale) + (r.bgenh ? " (probabilities that add up to more than 1)" : "") + ": the LD matrix of such dosages is not built.");
+    ldcheck(rg_ld_append_int(ld, g16.data(), n, bs, 0, scale, cols.data()));
+  }
+  if (dos && r.bgenh) sout << "     - " << dev_blocks << " blocks decoded on the device, " << host_blocks << " on the host\n";
+  for (int b = 0; !dos && b < nchunks; ++b) {
     const int64_t j0 = (int64_t)b * p.bsize;
     const int bs = (int)std::min<int64_t>(p.bsize, (int64_t)present.size() - j0);
     sout << "  block [" << b + 1 << "/" << nchunks << "] : reading in genotypes..." << std::flush;
@@ -155,7 +263,7 @@ static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
     sout << "done\n";
   }
 
-  sout << "\n** computing LD matrix **\n";
+  if (!dos) sout << "\n** computing LD matrix **\n";
   {  // write_snplist (Data.cpp:3862-3885)
     std::ofstream f(out + ".snplist");
     if (!f) throw std::runtime_error("cannot write file : " + out + ".snplist");

@@ -1,4 +1,4 @@
-"""The Step-2 LD matrix of a region (`regenie --step 2 --compute-corr`, hard calls): ctypes wrapper over include/rg_ld.h
+"""The Step-2 LD matrix of a region (`regenie --step 2 --compute-corr`, hard calls or integer dosages): ctypes wrapper over include/rg_ld.h
 (regenie_amd/csrc/ld_corr.hip).  `append` is what Data::get_G_svs does per block (Data.cpp:4227-4304), `finish` is
 Data::print_ld (Data.cpp:4368-4449).  No CPU path: without the HIP library or a GPU the constructor raises."""
 from __future__ import annotations
@@ -88,6 +88,28 @@ class LDMatrix:
             raise ValueError("append: one column index per row")
         self._check(self.lib.rg_ld_append(self.h, ptr, ld, bs, on_device, 1 if flip else 0, cols.ctypes.data))
 
+    def append_int(self, rows_u16, cols, scale: int) -> None:
+        """rows_u16 [bs][>= n] uint16 dosages in units of 1 / scale, 0xFFFF = missing (numpy, or a CUDA torch tensor of 2-byte
+        elements read in place); cols [bs]: the column of the matrix each row takes."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        rows, on_device = rows_u16, 0
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.uint16)
+            if rows.ndim != 2:
+                raise ValueError("append_int: rows must be 2-d")
+            bs, ld, ptr = rows.shape[0], rows.shape[1], rows.ctypes.data
+        else:
+            if not (rows.is_cuda and rows.element_size() == 2 and rows.dim() == 2 and rows.stride(1) == 1):
+                raise ValueError("append_int: device rows must be a 2-d CUDA tensor of 2-byte elements with unit stride")
+            bs, ld, ptr, on_device = rows.shape[0], rows.stride(0), rows.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(rows.device).synchronize()   # the library runs on its own stream
+        if rows.shape[1] < self.n:
+            raise ValueError("append_int: rows must hold n dosages")
+        if cols.shape != (bs,):
+            raise ValueError("append_int: one column index per row")
+        self._check(self.lib.rg_ld_append_int(self.h, ptr, ld, bs, on_device, int(scale), cols.ctypes.data))
+
     def finish(self, form: int = CORR_F64, tol: float = TOL, numtol: float = NUMTOL) -> np.ndarray:
         """R2_U16 -> uint16 [M (M - 1) / 2] (the binary .corr body, quantised on the device); CORR_F64 / COV_F64 -> float64 [M][M]."""
         M = self.M
@@ -99,6 +121,12 @@ class LDMatrix:
         """Raw integer sums of rows [a0, a0 + na) against rows [b0, b0 + nb) in append order: A = g0 . g0, B = g0 . miss, Bt = miss . g0, D = miss . miss."""
         res = {k: np.empty((max(na, 0), max(nb, 0)), np.int32) for k in ("A", "B", "Bt", "D")}
         self._check(self.lib.rg_ld_pair_sums(self.h, int(a0), int(na), int(b0), int(nb), *[res[k].ctypes.data for k in ("A", "B", "Bt", "D")]))
+        return res
+
+    def pair_sums_int(self, a0: int, na: int, b0: int, nb: int) -> dict:
+        """pair_sums for integer-dosage panels: int64 sums with g0 in integer units."""
+        res = {k: np.empty((max(na, 0), max(nb, 0)), np.int64) for k in ("A", "B", "Bt", "D")}
+        self._check(self.lib.rg_ld_pair_sums_int(self.h, int(a0), int(na), int(b0), int(nb), *[res[k].ctypes.data for k in ("A", "B", "Bt", "D")]))
         return res
 
     @property

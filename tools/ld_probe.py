@@ -4,7 +4,12 @@
 second.  With --driver DIR it also writes a .bed of the same size there and times `regenie-amd --step 2 --compute-corr` on it, and
 `oracle/_ref/regenie` on the same files when that binary exists (--ref-threads).
 
-  python tools/ld_probe.py --n 200000 --M 4096 [--miss 0.01] [--bsize 1024] [--driver DIR --ref-threads 16]"""
+With --dosage SCALE the panels are random integer dosages in units of 1 / SCALE generated on the device (uniform on [0, 2 SCALE], --miss
+of them missing) and appended in place through append_int; --driver then writes an 8-bit zlib BGEN of the same size (scale 255 only)
+and times `--compute-corr --ld-dosages`.  The effective rate 2 * 128^2 * n * tiles / time counts one multiply-add per sample pair of
+a tile whatever the number of digit planes: the figure to hold against an fp64 matrix-core Gram.
+
+  python tools/ld_probe.py --n 200000 --M 4096 [--miss 0.01] [--bsize 1024] [--dosage SCALE] [--driver DIR --ref-threads 16]"""
 import argparse
 import json
 import os
@@ -26,6 +31,7 @@ def main():
     ap.add_argument("--miss", type=float, default=0.01)
     ap.add_argument("--bsize", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--dosage", type=int, default=0)
     ap.add_argument("--driver", default=None)
     ap.add_argument("--ref-threads", type=int, default=16)
     ap.add_argument("--ref-timeout", type=int, default=600)
@@ -38,7 +44,14 @@ def main():
     X = np.linalg.qr(np.column_stack([np.ones(n), rng.normal(size=(n, a.C - 1))]))[0]
     g = torch.Generator(device="cuda").manual_seed(1)
     panels = []
-    for p0 in range(0, M, a.bsize):
+    for p0 in range(0, M if a.dosage else 0, a.bsize):
+        bs = min(a.bsize, M - p0)
+        v = torch.randint(0, 2 * a.dosage + 1, (bs, n), device="cuda", generator=g, dtype=torch.int32)
+        if a.miss > 0:
+            v[torch.rand((bs, n), device="cuda", generator=g) < a.miss] = 0xFFFF
+        panels.append(v.to(torch.int16).contiguous())      # (the 16 low bits: 0xFFFF and 2 * 16384 keep their pattern)
+        del v
+    for p0 in range(0, 0 if a.dosage else M, a.bsize):
         bs = min(a.bsize, M - p0)
         maf = torch.rand((bs, 1), device="cuda", generator=g) * 0.48 + 0.02
         u = torch.rand((bs, 4 * nb), device="cuda", generator=g)
@@ -50,22 +63,87 @@ def main():
         code = code.view(bs, nb, 4)
         panels.append((code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)).contiguous().cpu().numpy())
         del u, gt, code
-    res = {"n": n, "M": M, "C": a.C, "miss": a.miss, "bsize": a.bsize, "runs": []}
+    res = {"n": n, "M": M, "C": a.C, "miss": a.miss, "bsize": a.bsize, "dosage_scale": a.dosage, "runs": []}
+    nprod = 1 if not a.dosage else (2 if 2 * a.dosage <= 8127 else 3)      # digit planes of an operand
     for _ in range(a.reps):
         t0 = time.perf_counter()
         with LDMatrix(n, a.C, M) as ld:
             ld.set_basis(X.T)
             c0 = 0
             for rows in panels:
-                ld.append(rows, np.arange(c0, c0 + rows.shape[0]))
+                if a.dosage:
+                    ld.append_int(rows, np.arange(c0, c0 + rows.shape[0]), a.dosage)
+                else:
+                    ld.append(rows, np.arange(c0, c0 + rows.shape[0]))
                 c0 += rows.shape[0]
             t1 = time.perf_counter()
             ld.finish(R2_U16)
             t2 = time.perf_counter()
             ms, tiles = ld.kernel_ms, ld.tiles
         ops = 2.0 * tiles * 128 * 128 * ((n + 63) // 64 * 64)
-        res["runs"].append({"append_s": t1 - t0, "finish_s": t2 - t1, "gram_ms": ms, "tiles": tiles, "gram_int_ops_per_s": ops / (ms * 1e-3)})
-    if a.driver:
+        run = {"append_s": t1 - t0, "finish_s": t2 - t1, "gram_ms": ms, "tiles": tiles, "gram_int_ops_per_s": ops / (ms * 1e-3)}
+        if a.dosage:      # `tiles` counts 128 x 128 sums (A, B, Bt, D); an A tile runs nprod^2 plane products, a B tile nprod, a D tile one
+            npair = ((M + 127) // 128) * ((M + 127) // 128 + 1) // 2
+            rest = tiles - npair
+            nd = npair if rest > 0 else 0      # with missing values in every tile: D per pair, B per pair and the mirrored B off the diagonal
+            products = npair * nprod * nprod + (rest - nd) * nprod + nd
+            run["gram_int_ops_per_s"] = 2.0 * products * 128 * 128 * ((n + 63) // 64 * 64) / (ms * 1e-3)
+            run["effective_ops_per_s"] = 2.0 * tiles * 128 * 128 * n / (ms * 1e-3)
+            run["plane_products"] = products
+        res["runs"].append(run)
+    if a.driver and a.dosage:
+        import struct
+        import zlib
+        if a.dosage != 255:
+            raise SystemExit("--driver with --dosage writes an 8-bit BGEN: scale 255")
+        os.makedirs(a.driver, exist_ok=True)
+        pre = os.path.join(a.driver, "ldprobe")
+        with open(pre + ".bgen", "wb") as f:
+            ids = b"".join(struct.pack("<H", len(s)) + s for s in (("%d_%d" % (i + 1, i + 1)).encode() for i in range(n)))
+            sblock = struct.pack("<II", 8 + len(ids), n) + ids
+            header = struct.pack("<III", 20, M, n) + b"bgen" + struct.pack("<I", 1 | (2 << 2) | (1 << 31))
+            f.write(struct.pack("<I", len(header) + len(sblock)) + header + sblock)
+            j = 0
+            for rows in panels:
+                q = rows.cpu().numpy().view(np.uint16)
+                for r in q:      # dosage q = prob1 + 2 prob0 in units of 1 / 255: prob0 = q // 2, prob1 = q % 2 (+ 2 where prob0 allows, so that it is fractional)
+                    miss = r == 0xFFFF
+                    b0 = np.where(miss, 0, r // 2).astype(np.int64)
+                    b1 = np.where(miss, 0, r % 2).astype(np.int64)
+                    sh = (b0 > 0) & (b0 + b1 + 1 <= 255) & ~miss
+                    b0 -= sh; b1 += 2 * sh
+                    blk = struct.pack("<IHBB", n, 2, 2, 2) + np.where(miss, 0x82, 0x02).astype(np.uint8).tobytes() + bytes([0, 8])
+                    blk += np.stack([b0, b1], axis=1).astype(np.uint8).tobytes()
+                    z = zlib.compress(blk, 1)
+                    rs = ("v%d" % (j + 1)).encode()
+                    rec = struct.pack("<H", 0) + struct.pack("<H", len(rs)) + rs + struct.pack("<H", 1) + b"1" + struct.pack("<IH", j + 1, 2)
+                    rec += struct.pack("<I", 1) + b"A" + struct.pack("<I", 1) + b"G" + struct.pack("<II", len(z) + 4, len(blk)) + z
+                    f.write(rec)
+                    j += 1
+        with open(pre + ".covar", "w") as f:
+            f.write("FID IID V1 V2\n")
+            cv = rng.normal(size=(n, 2))
+            for i in range(n):
+                f.write("%d %d %.5f %.5f\n" % (i + 1, i + 1, cv[i, 0], cv[i, 1]))
+        common = ["--step", "2", "--bgen", pre + ".bgen", "--covarFile", pre + ".covar", "--bsize", str(a.bsize), "--compute-corr"]
+        t0 = time.perf_counter()
+        r = subprocess.run([os.path.join(ROOT, "regenie_amd", "bin", "regenie-amd")] + common + ["--ld-dosages", "--out", pre + "_amd"], capture_output=True, text=True)
+        res["driver_wall_s"] = time.perf_counter() - t0
+        res["driver_rc"] = r.returncode
+        res["driver_tail"] = r.stdout[-400:]
+        ref = os.path.join(ROOT, "oracle", "_ref", "regenie")
+        if os.path.exists(ref):
+            t0 = time.perf_counter()
+            try:
+                rr = subprocess.run([ref] + common + ["--threads", str(a.ref_threads), "--out", pre + "_ref"], capture_output=True, text=True, timeout=a.ref_timeout)
+                res["reference_wall_s"], res["reference_rc"] = time.perf_counter() - t0, rr.returncode
+                if rr.returncode == 0 and r.returncode == 0:
+                    x = np.fromfile(pre + "_amd.corr", np.uint16)
+                    y = np.fromfile(pre + "_ref.corr", np.uint16)
+                    res["values_differing_from_reference"] = int((x != y).sum()) if x.shape == y.shape else -1
+            except subprocess.TimeoutExpired:
+                res["reference_wall_s"] = "> %d (stopped)" % a.ref_timeout
+    elif a.driver:
         os.makedirs(a.driver, exist_ok=True)
         pre = os.path.join(a.driver, "ldprobe")
         with open(pre + ".bed", "wb") as f:

@@ -104,22 +104,14 @@ __device__ __forceinline__ void ld_tile(const uint8_t* __restrict__ A, int a_row
       }
 }
 
-// grid.x = tile pair, grid.y = which sum (0: A, 1: B, 2: B of the mirrored pair / Bt, 3: D).
-//   tri != 0 (rg_ld_finish): rows [0, na) against themselves, tile pairs tr <= tc only; SA, SD [na][na] (upper tiles written),
-//     SB [na][na] full: y = 1 writes tile (tr, tc) of it, y = 2 tile (tc, tr); tile_miss[t] != 0: tile t has a missing call.
-//   kinds: bit k set = sum k is wanted.
-//   tri == 0 (rg_ld_pair_sums): rows [a0, a0 + na) against [b0, b0 + nb), every tile pair and every sum; SBt [na][nb] is y = 2.
-__global__ __launch_bounds__(256) void k_ld_gram(const uint8_t* __restrict__ rows, int64_t ld, int a0, int na, int b0, int nb, int tri, int kinds,
-                                                 const uint8_t* __restrict__ tile_miss, int32_t* SA, int32_t* SB, int32_t* SBt, int32_t* SD, int64_t ldc) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * 2 * LT * LPITCH];
-  const int nta = (na + LT - 1) / LT, ntb = (nb + LT - 1) / LT;
+// The tile pair (tr, tc) of workgroup blockIdx.x over nta x ntb tiles; tri: pairs tr <= tc only.  false: no such pair.
+__device__ __forceinline__ bool ld_tile_pair(int nta, int ntb, int tri, int& tr, int& tc) {
   int tidx = blockIdx.x;
   {  // XCD-aware remap (gram_i8.hip): consecutive tile ids share an operand panel; keep them on one XCD's L2
     const int nwg = gridDim.x;
     const int q = nwg / 8, r = nwg % 8, xcd = tidx % 8, k = tidx / 8;
     tidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
   }
-  int tr, tc;
   if (tri) {  // unrank over tc >= tr: pair index = tc (tc + 1) / 2 + tr
     tc = (int)((sqrtf(8.0f * tidx + 1.0f) - 1.0f) * 0.5f);
     while ((tc + 1) * (tc + 2) / 2 <= tidx) ++tc;
@@ -129,29 +121,59 @@ __global__ __launch_bounds__(256) void k_ld_gram(const uint8_t* __restrict__ row
     tr = tidx / ntb;
     tc = tidx - tr * ntb;
   }
-  if (tr >= nta || tc >= ntb) return;
+  return tr < nta && tc < ntb;
+}
+
+// The body of the Gram kernels: grid.x = tile pair, grid.y = which sum (0: A, 1: B, 2: B of the mirrored pair / Bt, 3: D).
+//   tri != 0 (rg_ld_finish): rows [0, na) against themselves, tile pairs tr <= tc only; SA, SD [na][na] (upper tiles written),
+//     SB [na][na] full: y = 1 writes tile (tr, tc) of it, y = 2 tile (tc, tr); tile_miss[t] != 0: tile t has a missing call.
+//   kinds: bit k set = sum k is wanted.
+//   tri == 0 (rg_ld_pair_sums): rows [a0, a0 + na) against [b0, b0 + nb), every tile pair and every sum; SBt [na][nb] is y = 2.
+// Store: the row store and its tile routine -- run<MA, MB>(ra, a_rows, rb, b_rows, same, C, ldc, smem): the tile of the rows from ra on
+// against the rows from rb on into C; MA / MB: the operand is the missing indicator of its rows, not their dosage.
+template <class Store, class Sum = typename Store::Sum>
+__device__ __forceinline__ void ld_sums(const Store& s, int a0, int na, int b0, int nb, int tri, int kinds, const uint8_t* __restrict__ tile_miss, Sum* SA, Sum* SB,
+                                        Sum* SBt, Sum* SD, int64_t ldc, uint8_t* smem) {
+  int tr, tc;
+  if (!ld_tile_pair((na + LT - 1) / LT, (nb + LT - 1) / LT, tri, tr, tc)) return;
   const int kind = blockIdx.y;
   if (!((kinds >> kind) & 1)) return;      // a sum the caller did not ask for
-  const uint8_t* Ar = rows + (int64_t)(a0 + tr * LT) * ld;
-  const uint8_t* Bc = rows + (int64_t)(b0 + tc * LT) * ld;
+  const int ra = a0 + tr * LT, rb = b0 + tc * LT;
   const int ar = min(LT, na - tr * LT), bc = min(LT, nb - tc * LT);
   const bool diag = tri && tr == tc;
+  const int64_t at = (int64_t)tr * LT * ldc + (int64_t)tc * LT;      // tile (tr, tc) of an output
   if (kind == 0) {
-    ld_tile(Ar, ar, LD_LUT_DOSAGE, Bc, bc, LD_LUT_DOSAGE, diag, ld, SA + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+    s.template run<false, false>(ra, ar, rb, bc, diag, SA + at, ldc, smem);
   } else if (kind == 1) {
     if (tile_miss && !tile_miss[tc]) return;
-    ld_tile(Ar, ar, LD_LUT_DOSAGE, Bc, bc, LD_LUT_MISS, false, ld, SB + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+    s.template run<false, true>(ra, ar, rb, bc, false, SB + at, ldc, smem);
   } else if (kind == 2) {
     if (tri) {  // B of the mirrored pair: dosage of tile tc against the indicator of tile tr
       if (diag || (tile_miss && !tile_miss[tr])) return;
-      ld_tile(Bc, bc, LD_LUT_DOSAGE, Ar, ar, LD_LUT_MISS, false, ld, SB + (int64_t)tc * LT * ldc + (int64_t)tr * LT, ldc, smem);
+      s.template run<false, true>(rb, bc, ra, ar, false, SB + (int64_t)tc * LT * ldc + (int64_t)tr * LT, ldc, smem);
     } else {
-      ld_tile(Ar, ar, LD_LUT_MISS, Bc, bc, LD_LUT_DOSAGE, false, ld, SBt + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+      s.template run<true, false>(ra, ar, rb, bc, false, SBt + at, ldc, smem);
     }
   } else {
     if (tile_miss && !(tile_miss[tr] && tile_miss[tc])) return;
-    ld_tile(Ar, ar, LD_LUT_MISS, Bc, bc, LD_LUT_MISS, diag, ld, SD + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
+    s.template run<true, true>(ra, ar, rb, bc, diag, SD + at, ldc, smem);
   }
+}
+
+struct LdRows {      // the 2-bit row store: the LUT that expands the codes makes an operand the dosage or the indicator
+  using Sum = int32_t;
+  const uint8_t* rows;
+  int64_t ld;
+  template <bool MA, bool MB>
+  __device__ __forceinline__ void run(int ra, int a_rows, int rb, int b_rows, bool same, Sum* C, int64_t ldc, uint8_t* smem) const {
+    ld_tile(rows + (int64_t)ra * ld, a_rows, MA ? LD_LUT_MISS : LD_LUT_DOSAGE, rows + (int64_t)rb * ld, b_rows, MB ? LD_LUT_MISS : LD_LUT_DOSAGE, same, ld, C, ldc, smem);
+  }
+};
+
+__global__ __launch_bounds__(256) void k_ld_gram(const uint8_t* __restrict__ rows, int64_t ld, int a0, int na, int b0, int nb, int tri, int kinds,
+                                                 const uint8_t* __restrict__ tile_miss, int32_t* SA, int32_t* SB, int32_t* SBt, int32_t* SD, int64_t ldc) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * 2 * LT * LPITCH];
+  ld_sums(LdRows{rows, ld}, a0, na, b0, nb, tri, kinds, tile_miss, SA, SB, SBt, SD, ldc, smem);
 }
 
 // Rows as they arrive (nbytes = ceil(n / 4) bytes used, ld bytes apart, already copied into the store) -> the store's form:
@@ -310,54 +332,25 @@ __device__ __forceinline__ void ldi_tile(const int8_t* __restrict__ A, int a_row
 }
 
 // k_ld_gram for the plane store: the same grid, tile-pair order and meaning of tri, kinds, tile_miss and the four sums (64-bit
-// here); row r of the matrix is row r of every plane.
+// here); row r of the matrix is row r of every plane: of the NP digit planes for the dosage, of the one after them for the indicator.
+template <int NP>
+struct LdPlanes {
+  using Sum = long long;
+  const int8_t* planes;
+  int64_t Kp, ps;
+  template <bool MA, bool MB>
+  __device__ __forceinline__ void run(int ra, int a_rows, int rb, int b_rows, bool same, Sum* C, int64_t ldc, uint8_t* smem) const {
+    ldi_tile<MA ? 1 : NP, MB ? 1 : NP>(planes + (int64_t)ra * Kp + (MA ? NP * ps : 0), a_rows, planes + (int64_t)rb * Kp + (MB ? NP * ps : 0), b_rows, same, Kp, ps, C,
+                                       ldc, smem);
+  }
+};
+
 template <int NP>
 __global__ __launch_bounds__(512) void k_ld_gram_int(const int8_t* __restrict__ planes, int64_t Kp, int64_t ps, int a0, int na, int b0, int nb, int tri,
                                                      int kinds, const uint8_t* __restrict__ tile_miss, long long* SA, long long* SB, long long* SBt,
                                                      long long* SD, int64_t ldc) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[2 * NP * LT * LPITCH];
-  const int nta = (na + LT - 1) / LT, ntb = (nb + LT - 1) / LT;
-  int tidx = blockIdx.x;
-  {  // XCD-aware remap, as k_ld_gram
-    const int nwg = gridDim.x;
-    const int q = nwg / 8, r = nwg % 8, xcd = tidx % 8, k = tidx / 8;
-    tidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
-  int tr, tc;
-  if (tri) {
-    tc = (int)((sqrtf(8.0f * tidx + 1.0f) - 1.0f) * 0.5f);
-    while ((tc + 1) * (tc + 2) / 2 <= tidx) ++tc;
-    while (tc * (tc + 1) / 2 > tidx) --tc;
-    tr = tidx - tc * (tc + 1) / 2;
-  } else {
-    tr = tidx / ntb;
-    tc = tidx - tr * ntb;
-  }
-  if (tr >= nta || tc >= ntb) return;
-  const int kind = blockIdx.y;
-  if (!((kinds >> kind) & 1)) return;
-  const int8_t* Ar = planes + (int64_t)(a0 + tr * LT) * Kp;
-  const int8_t* Bc = planes + (int64_t)(b0 + tc * LT) * Kp;
-  const int8_t* Am = Ar + NP * ps;
-  const int8_t* Bm = Bc + NP * ps;
-  const int ar = min(LT, na - tr * LT), bc = min(LT, nb - tc * LT);
-  const bool diag = tri && tr == tc;
-  if (kind == 0) {
-    ldi_tile<NP, NP>(Ar, ar, Bc, bc, diag, Kp, ps, SA + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
-  } else if (kind == 1) {
-    if (tile_miss && !tile_miss[tc]) return;
-    ldi_tile<NP, 1>(Ar, ar, Bm, bc, false, Kp, ps, SB + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
-  } else if (kind == 2) {
-    if (tri) {
-      if (diag || (tile_miss && !tile_miss[tr])) return;
-      ldi_tile<NP, 1>(Bc, bc, Am, ar, false, Kp, ps, SB + (int64_t)tc * LT * ldc + (int64_t)tr * LT, ldc, smem);
-    } else {
-      ldi_tile<1, NP>(Am, ar, Bc, bc, false, Kp, ps, SBt + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
-    }
-  } else {
-    if (tile_miss && !(tile_miss[tr] && tile_miss[tc])) return;
-    ldi_tile<1, 1>(Am, ar, Bm, bc, diag, Kp, ps, SD + (int64_t)tr * LT * ldc + (int64_t)tc * LT, ldc, smem);
-  }
+  ld_sums(LdPlanes<NP>{planes, Kp, ps}, a0, na, b0, nb, tri, kinds, tile_miss, SA, SB, SBt, SD, ldc, smem);
 }
 
 
@@ -430,6 +423,8 @@ __global__ __launch_bounds__(256) void k_ld_r2(const double* __restrict__ LD, in
 
 }  // namespace
 
+enum { LD_EMPTY = 0, LD_CALLS, LD_INTS };
+
 struct rg_ld_ctx {
   int dev = 0;
   int64_t n = 0, ld = 0;
@@ -437,7 +432,7 @@ struct rg_ld_ctx {
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   uint8_t* rows = nullptr;            // [M][ld] in the order appended
-  int kind = 0;                       // 0: no panel yet, 1: 2-bit hard calls (rows), 2: integer dosages (planes)
+  int kind = LD_EMPTY;                // the store in use: no panel yet, 2-bit hard calls (rows), integer dosages (planes)
   int scale = 0, np = 0;              // integer dosages: units of 1 / scale, np digit planes
   int64_t kp = 0;                     // n rounded up to 64
   int8_t* planes = nullptr;           // [planes_np + 1][M][kp], allocated by the first rg_ld_append_int
@@ -470,6 +465,73 @@ struct DevBuf {  // device memory of one call
   template <class T> T* as() const { return (T*)p; }
 };
 }  // namespace
+
+// The Gram kernel of the store the context holds (hard calls, two or three digit planes), on the context's stream.  The outputs are
+// [na][nb] of the store's sum type (int32_t / long long).
+static void ld_launch_gram(rg_ld_ctx* ctx, dim3 grid, int a0, int na, int b0, int nb, int tri, int kinds, const uint8_t* tile_miss, void* SA, void* SB, void* SBt,
+                           void* SD) {
+  if (ctx->kind == LD_CALLS) {
+    hipLaunchKernelGGL(k_ld_gram, grid, dim3(256), 0, ctx->st, ctx->rows, ctx->ld, a0, na, b0, nb, tri, kinds, tile_miss, (int32_t*)SA, (int32_t*)SB, (int32_t*)SBt,
+                       (int32_t*)SD, (int64_t)nb);
+  } else {
+    const auto k = ctx->np == 2 ? k_ld_gram_int<2> : k_ld_gram_int<3>;
+    hipLaunchKernelGGL(k, grid, dim3(512), 0, ctx->st, ctx->planes, ctx->kp, (int64_t)ctx->M * ctx->kp, a0, na, b0, nb, tri, kinds, tile_miss, (long long*)SA,
+                       (long long*)SB, (long long*)SBt, (long long*)SD, (int64_t)nb);
+  }
+}
+
+// rg_ld_pair_sums / rg_ld_pair_sums_int after their argument checks; T: the sum type of the store
+template <class T>
+static int ld_pair_sums(rg_ld_ctx* ctx, int a0, int na, int b0, int nb, T* const (&outs)[4]) {
+  LD_HIP(hipSetDevice(ctx->dev));
+  const size_t cnt = (size_t)na * nb;
+  DevBuf S;
+  LD_HIP(S.alloc(4 * cnt * sizeof(T)));
+  T* s = S.as<T>();
+  const int nt = ((na + LT - 1) / LT) * ((nb + LT - 1) / LT);
+  const int kinds = (outs[0] ? 1 : 0) | (outs[1] ? 2 : 0) | (outs[2] ? 4 : 0) | (outs[3] ? 8 : 0);
+  LD_HIP(hipEventRecord(ctx->e0, ctx->st));
+  ld_launch_gram(ctx, dim3(nt, 4), a0, na, b0, nb, 0, kinds, nullptr, s, s + cnt, s + 2 * cnt, s + 3 * cnt);
+  LD_HIP(hipGetLastError());
+  LD_HIP(hipEventRecord(ctx->e1, ctx->st));
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) LD_HIP(hipMemcpyAsync(outs[k], s + k * cnt, cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
+  float ms = 0.f;
+  LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+  ctx->last_ms = ms;
+  ctx->last_tiles = (int64_t)nt * __builtin_popcount(kinds);
+  return RG_LD_OK;
+}
+
+// What the two append entries check alike, after their own arguments: room for bs more rows, every column in range and open.
+static int ld_append_check(rg_ld_ctx* ctx, const std::string& who, int32_t bs, const int32_t* cols) {
+  if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, who + ": more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
+  std::vector<uint8_t> seen(ctx->col_state);
+  for (int j = 0; j < bs; ++j) {
+    if (cols[j] < 0 || cols[j] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, who + ": column index out of range");
+    if (seen[cols[j]]) return ld_fail(ctx, RG_LD_ERR_ARG, who + ": column " + std::to_string(cols[j]) + " is used twice");
+    seen[cols[j]] = 1;
+  }
+  return RG_LD_OK;
+}
+
+// The bs rows just stored become rows of the matrix.  Without a basis (rg_ld_set_basis) obs and sums are empty; otherwise obs [bs][2]:
+// per row the sum (genotype units) and the number of its observed entries; sums [bs][2][C]: X^T g0 and X^T miss in genotype units.
+static void ld_append_commit(rg_ld_ctx* ctx, int32_t bs, const int32_t* cols, const std::vector<double>& obs, const std::vector<double>& sums) {
+  const int r0 = ctx->nrows, C = ctx->C;
+  ctx->mean.resize((size_t)r0 + bs, 0.0);
+  ctx->nmiss.resize((size_t)r0 + bs, 0);
+  ctx->gx.resize(((size_t)r0 + bs) * C, 0.0);
+  for (int j = 0; j < bs && !obs.empty(); ++j) {
+    const double nobs = obs[2 * j + 1], m = nobs > 0 ? obs[2 * j] / nobs : 0.0;
+    ctx->mean[r0 + j] = m;
+    ctx->nmiss[r0 + j] = (int32_t)(ctx->n - (int64_t)nobs);
+    for (int c = 0; c < C; ++c) ctx->gx[(size_t)(r0 + j) * C + c] = sums[((size_t)j * 2) * C + c] + m * sums[((size_t)j * 2 + 1) * C + c];
+  }
+  for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
+  ctx->nrows += bs;
+}
 
 extern "C" {
 
@@ -546,44 +608,30 @@ int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, in
   if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: context was not created");
   const int64_t n = ctx->n, nbytes = (n + 3) / 4;
   if (!rows || !cols || bs < 1 || ld < nbytes) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: bad arguments (need bs >= 1, ld >= ceil(n / 4))");
-  if (ctx->kind == 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: the matrix holds integer-dosage panels (rg_ld_append_int); the two kinds cannot be mixed");
-  if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
-  {
-    std::vector<uint8_t> seen(ctx->col_state);
-    for (int j = 0; j < bs; ++j) {
-      if (cols[j] < 0 || cols[j] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: column index out of range");
-      if (seen[cols[j]]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: column " + std::to_string(cols[j]) + " is used twice");
-      seen[cols[j]] = 1;
-    }
-  }
+  if (ctx->kind == LD_INTS) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append: the matrix holds integer-dosage panels (rg_ld_append_int); the two kinds cannot be mixed");
+  if (int rc = ld_append_check(ctx, "rg_ld_append", bs, cols)) return rc;
   LD_HIP(hipSetDevice(ctx->dev));
   uint8_t* dst = ctx->rows + (int64_t)ctx->nrows * ctx->ld;
   LD_HIP(hipMemcpy2DAsync(dst, ctx->ld, rows, ld, nbytes, bs, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
   hipLaunchKernelGGL(k_ld_store, dim3(bs), dim3(256), 0, ctx->st, dst, ctx->ld, n, flip ? 1 : 0);
   LD_HIP(hipGetLastError());
   LD_HIP(hipStreamSynchronize(ctx->st));
-  const int r0 = ctx->nrows, C = ctx->C;
-  ctx->mean.resize((size_t)r0 + bs, 0.0);
-  ctx->nmiss.resize((size_t)r0 + bs, 0);
-  ctx->gx.resize(((size_t)r0 + bs) * C, 0.0);
+  std::vector<double> obs, sums;
   if (ctx->s2) {  // X^T g0, X^T miss and the call counts of the stored rows (the allele is already the one counted)
-    std::vector<double> sums((size_t)bs * 2 * C);
+    obs.resize((size_t)bs * 2);
+    sums.resize((size_t)bs * 2 * ctx->C);
     std::vector<int32_t> counts((size_t)bs * 4);
     rg_s2_contract_out co = {sums.data(), nullptr, counts.data(), nullptr};
     if (rg_s2_contract_packed(ctx->s2, dst, ctx->ld, bs, 1, 0, &co) != RG_S2_OK)
       return ld_fail(ctx, RG_LD_ERR_HIP, std::string("rg_ld_append: ") + rg_s2_last_error(ctx->s2));
     for (int j = 0; j < bs; ++j) {
       const int32_t* c4 = counts.data() + (size_t)j * 4;
-      const int64_t nobs = n - c4[2];
-      const double m = nobs > 0 ? (double)((int64_t)c4[0] + 2 * (int64_t)c4[1]) / (double)nobs : 0.0;
-      ctx->mean[r0 + j] = m;
-      ctx->nmiss[r0 + j] = c4[2];
-      for (int c = 0; c < C; ++c) ctx->gx[(size_t)(r0 + j) * C + c] = sums[((size_t)j * 2) * C + c] + m * sums[((size_t)j * 2 + 1) * C + c];
+      obs[2 * j] = (double)((int64_t)c4[0] + 2 * (int64_t)c4[1]);
+      obs[2 * j + 1] = (double)(n - c4[2]);
     }
   }
-  for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
-  ctx->nrows += bs;
-  ctx->kind = 1;
+  ld_append_commit(ctx, bs, cols, obs, sums);
+  ctx->kind = LD_CALLS;
   return RG_LD_OK;
 }
 
@@ -592,18 +640,10 @@ int rg_ld_append_int(rg_ld_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, 
   const int64_t n = ctx->n;
   if (!G || !cols || bs < 1 || ld < n) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: bad arguments (need bs >= 1, ld >= n)");
   if (scale < 1 || scale > 16384) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: need 1 <= scale <= 16384");
-  if (ctx->kind == 1) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the matrix holds 2-bit panels (rg_ld_append); the two kinds cannot be mixed");
-  if (ctx->kind == 2 && scale != ctx->scale)
+  if (ctx->kind == LD_CALLS) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the matrix holds 2-bit panels (rg_ld_append); the two kinds cannot be mixed");
+  if (ctx->kind == LD_INTS && scale != ctx->scale)
     return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: the matrix holds panels of scale " + std::to_string(ctx->scale) + "; one matrix has one scale");
-  if ((int64_t)ctx->nrows + bs > ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: more rows than the " + std::to_string(ctx->M) + " columns of the matrix");
-  {
-    std::vector<uint8_t> seen(ctx->col_state);
-    for (int j = 0; j < bs; ++j) {
-      if (cols[j] < 0 || cols[j] >= ctx->M) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: column index out of range");
-      if (seen[cols[j]]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: column " + std::to_string(cols[j]) + " is used twice");
-      seen[cols[j]] = 1;
-    }
-  }
+  if (int rc = ld_append_check(ctx, "rg_ld_append_int", bs, cols)) return rc;
   LD_HIP(hipSetDevice(ctx->dev));
   const int np = 2 * scale <= 8127 ? 2 : 3;      // the rule of rg_s2_qt_block_int: two balanced base-128 digits reach 63 + 63 * 128
   const int64_t kp = ctx->kp, ps = (int64_t)ctx->M * kp;
@@ -639,88 +679,35 @@ int rg_ld_append_int(rg_ld_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, 
   LD_HIP(hipMemcpyAsync(&bad, dBad.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
   LD_HIP(hipStreamSynchronize(ctx->st));
   if (bad) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_append_int: a dosage is above 2 * scale = " + std::to_string(2 * scale) + " (0xFFFF is the missing value)");
-  const int r0 = ctx->nrows, C = ctx->C;
-  ctx->mean.resize((size_t)r0 + bs, 0.0);
-  ctx->nmiss.resize((size_t)r0 + bs, 0);
-  ctx->gx.resize(((size_t)r0 + bs) * C, 0.0);
+  std::vector<double> obs, sums;
   if (ctx->s2) {  // X^T g0 and X^T miss in genotype units, the sum and the number of the observed entries
-    std::vector<double> sums((size_t)bs * 2 * C), vstat((size_t)bs * 4);
+    obs.resize((size_t)bs * 2);
+    sums.resize((size_t)bs * 2 * ctx->C);
+    std::vector<double> vstat((size_t)bs * 4);
     rg_s2_contract_out co = {sums.data(), nullptr, nullptr, vstat.data()};
     if (rg_s2_contract_int(ctx->s2, src, lds, bs, 1, scale, &co) != RG_S2_OK)
       return ld_fail(ctx, RG_LD_ERR_HIP, std::string("rg_ld_append_int: ") + rg_s2_last_error(ctx->s2));
-    for (int j = 0; j < bs; ++j) {
-      const double* v4 = vstat.data() + (size_t)j * 4;
-      const double m = v4[2] > 0 ? v4[0] / (double)scale / v4[2] : 0.0;
-      ctx->mean[r0 + j] = m;
-      ctx->nmiss[r0 + j] = (int32_t)(n - (int64_t)v4[2]);
-      for (int c = 0; c < C; ++c) ctx->gx[(size_t)(r0 + j) * C + c] = sums[((size_t)j * 2) * C + c] + m * sums[((size_t)j * 2 + 1) * C + c];
-    }
+    for (int j = 0; j < bs; ++j) { obs[2 * j] = vstat[(size_t)j * 4] / (double)scale; obs[2 * j + 1] = vstat[(size_t)j * 4 + 2]; }
   }
-  for (int j = 0; j < bs; ++j) { ctx->col_of_row.push_back(cols[j]); ctx->col_state[cols[j]] = 1; }
-  ctx->nrows += bs;
-  ctx->kind = 2; ctx->scale = scale; ctx->np = np;
+  ld_append_commit(ctx, bs, cols, obs, sums);
+  ctx->kind = LD_INTS; ctx->scale = scale; ctx->np = np;
   return RG_LD_OK;
 }
 
 int rg_ld_pair_sums_int(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int64_t* A, int64_t* B, int64_t* Bt, int64_t* D) {
   if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: context was not created");
-  if (ctx->kind != 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: the matrix holds no integer-dosage panel");
+  if (ctx->kind != LD_INTS) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: the matrix holds no integer-dosage panel");
   if (a0 < 0 || b0 < 0 || na < 1 || nb < 1 || (int64_t)a0 + na > ctx->nrows || (int64_t)b0 + nb > ctx->nrows)
     return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums_int: row range outside the panels appended");
-  LD_HIP(hipSetDevice(ctx->dev));
-  const size_t cnt = (size_t)na * nb;
-  DevBuf S;
-  LD_HIP(S.alloc(4 * cnt * sizeof(long long)));
-  long long* s = S.as<long long>();
-  const int nt = ((na + LT - 1) / LT) * ((nb + LT - 1) / LT);
-  const int kinds = (A ? 1 : 0) | (B ? 2 : 0) | (Bt ? 4 : 0) | (D ? 8 : 0);
-  const int64_t ps = (int64_t)ctx->M * ctx->kp;
-  LD_HIP(hipEventRecord(ctx->e0, ctx->st));
-  if (ctx->np == 2)
-    hipLaunchKernelGGL(k_ld_gram_int<2>, dim3(nt, 4), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s,
-                       s + cnt, s + 2 * cnt, s + 3 * cnt, (int64_t)nb);
-  else
-    hipLaunchKernelGGL(k_ld_gram_int<3>, dim3(nt, 4), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s,
-                       s + cnt, s + 2 * cnt, s + 3 * cnt, (int64_t)nb);
-  LD_HIP(hipGetLastError());
-  LD_HIP(hipEventRecord(ctx->e1, ctx->st));
-  int64_t* outs[4] = {A, B, Bt, D};
-  for (int k = 0; k < 4; ++k)
-    if (outs[k]) LD_HIP(hipMemcpyAsync(outs[k], s + k * cnt, cnt * sizeof(long long), hipMemcpyDeviceToHost, ctx->st));
-  LD_HIP(hipStreamSynchronize(ctx->st));
-  float ms = 0.f;
-  LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
-  ctx->last_ms = ms;
-  ctx->last_tiles = (int64_t)nt * __builtin_popcount(kinds);
-  return RG_LD_OK;
+  return ld_pair_sums<int64_t>(ctx, a0, na, b0, nb, {A, B, Bt, D});
 }
 
 int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t nb, int32_t* A, int32_t* B, int32_t* Bt, int32_t* D) {
   if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: context was not created");
   if (a0 < 0 || b0 < 0 || na < 1 || nb < 1 || (int64_t)a0 + na > ctx->nrows || (int64_t)b0 + nb > ctx->nrows)
     return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: row range outside the panels appended");
-  if (ctx->kind == 2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: the matrix holds integer-dosage panels (rg_ld_pair_sums_int)");
-  LD_HIP(hipSetDevice(ctx->dev));
-  const size_t cnt = (size_t)na * nb;
-  DevBuf S;
-  LD_HIP(S.alloc(4 * cnt * sizeof(int32_t)));
-  int32_t* s = S.as<int32_t>();
-  const int nt = ((na + LT - 1) / LT) * ((nb + LT - 1) / LT);
-  const int kinds = (A ? 1 : 0) | (B ? 2 : 0) | (Bt ? 4 : 0) | (D ? 8 : 0);
-  LD_HIP(hipEventRecord(ctx->e0, ctx->st));
-  hipLaunchKernelGGL(k_ld_gram, dim3(nt, 4), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, a0, na, b0, nb, 0, kinds, (const uint8_t*)nullptr, s, s + cnt, s + 2 * cnt,
-                     s + 3 * cnt, (int64_t)nb);
-  LD_HIP(hipGetLastError());
-  LD_HIP(hipEventRecord(ctx->e1, ctx->st));
-  int32_t* outs[4] = {A, B, Bt, D};
-  for (int k = 0; k < 4; ++k)
-    if (outs[k]) LD_HIP(hipMemcpyAsync(outs[k], s + k * cnt, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
-  LD_HIP(hipStreamSynchronize(ctx->st));
-  float ms = 0.f;
-  LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
-  ctx->last_ms = ms;
-  ctx->last_tiles = (int64_t)nt * __builtin_popcount(kinds);
-  return RG_LD_OK;
+  if (ctx->kind == LD_INTS) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_pair_sums: the matrix holds integer-dosage panels (rg_ld_pair_sums_int)");
+  return ld_pair_sums<int32_t>(ctx, a0, na, b0, nb, {A, B, Bt, D});
 }
 
 int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol) {
@@ -742,8 +729,7 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
   LD_HIP(hipMemsetAsync(dLD.p, 0, MM * sizeof(double), ctx->st));
   ctx->last_ms = 0.0;
   ctx->last_tiles = 0;
-  const bool ints = ctx->kind == 2;
-  const size_t ssz = ints ? sizeof(long long) : sizeof(int32_t);
+  const size_t ssz = ctx->kind == LD_INTS ? sizeof(long long) : sizeof(int32_t);      // the sums of the store
   if (R > 0) {
     LD_HIP(dSA.alloc(RR * ssz));
     if (any_miss) {
@@ -762,16 +748,7 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
     LD_HIP(hipMemcpyAsync(dCol.p, ctx->col_of_row.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->st));
     const int npair = nt * (nt + 1) / 2;
     LD_HIP(hipEventRecord(ctx->e0, ctx->st));
-    const int64_t ps = (int64_t)M * ctx->kp;
-    if (!ints)
-      hipLaunchKernelGGL(k_ld_gram, dim3(npair, any_miss ? 4 : 1), dim3(256), 0, ctx->st, ctx->rows, ctx->ld, 0, R, 0, R, 1, 0xF, dTm.as<uint8_t>(), dSA.as<int32_t>(),
-                         dSB.as<int32_t>(), (int32_t*)nullptr, dSD.as<int32_t>(), (int64_t)R);
-    else if (ctx->np == 2)
-      hipLaunchKernelGGL(k_ld_gram_int<2>, dim3(npair, any_miss ? 4 : 1), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, 0, R, 0, R, 1, 0xF,
-                         (const uint8_t*)dTm.as<uint8_t>(), dSA.as<long long>(), dSB.as<long long>(), (long long*)nullptr, dSD.as<long long>(), (int64_t)R);
-    else
-      hipLaunchKernelGGL(k_ld_gram_int<3>, dim3(npair, any_miss ? 4 : 1), dim3(512), 0, ctx->st, (const int8_t*)ctx->planes, ctx->kp, ps, 0, R, 0, R, 1, 0xF,
-                         (const uint8_t*)dTm.as<uint8_t>(), dSA.as<long long>(), dSB.as<long long>(), (long long*)nullptr, dSD.as<long long>(), (int64_t)R);
+    ld_launch_gram(ctx, dim3(npair, any_miss ? 4 : 1), 0, R, 0, R, 1, 0xF, dTm.as<uint8_t>(), dSA.p, dSB.p, nullptr, dSD.p);
     LD_HIP(hipGetLastError());
     LD_HIP(hipEventRecord(ctx->e1, ctx->st));
     int64_t tiles = npair;
@@ -780,14 +757,12 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
         for (int b = a; b < nt; ++b) tiles += (tile_miss[b] ? 1 : 0) + ((a != b && tile_miss[a]) ? 1 : 0) + ((tile_miss[a] && tile_miss[b]) ? 1 : 0);
     ctx->last_tiles = tiles;
     const dim3 g2((R + 15) / 16, (R + 15) / 16);
-    if (!ints)
-      hipLaunchKernelGGL(k_ld_combine<int32_t>, g2, dim3(256), 0, ctx->st, (const int32_t*)dSA.as<int32_t>(), any_miss ? dSB.as<int32_t>() : (const int32_t*)nullptr,
-                         (const int32_t*)dSD.as<int32_t>(), R, 1.0, (const double*)dMean.as<double>(), (const double*)dGx.as<double>(), C,
-                         (const int32_t*)dCol.as<int32_t>(), dLD.as<double>(), M);
+    if (ctx->kind == LD_CALLS)      // (dSB, dSD are null without a missing call)
+      hipLaunchKernelGGL(k_ld_combine<int32_t>, g2, dim3(256), 0, ctx->st, dSA.as<int32_t>(), dSB.as<int32_t>(), dSD.as<int32_t>(), R, 1.0, dMean.as<double>(),
+                         dGx.as<double>(), C, dCol.as<int32_t>(), dLD.as<double>(), M);
     else
-      hipLaunchKernelGGL(k_ld_combine<long long>, g2, dim3(256), 0, ctx->st, (const long long*)dSA.as<long long>(),
-                         any_miss ? dSB.as<long long>() : (const long long*)nullptr, (const long long*)dSD.as<long long>(), R, (double)ctx->scale,
-                         (const double*)dMean.as<double>(), (const double*)dGx.as<double>(), C, (const int32_t*)dCol.as<int32_t>(), dLD.as<double>(), M);
+      hipLaunchKernelGGL(k_ld_combine<long long>, g2, dim3(256), 0, ctx->st, dSA.as<long long>(), dSB.as<long long>(), dSD.as<long long>(), R, (double)ctx->scale,
+                         dMean.as<double>(), dGx.as<double>(), C, dCol.as<int32_t>(), dLD.as<double>(), M);
     LD_HIP(hipGetLastError());
   }
   const dim3 gM((M + 15) / 16, (M + 15) / 16);

@@ -9,9 +9,7 @@ namespace rgdrv {
 // buildLookupTable (Geno.cpp:2833-2856): 00 -> 2, 01 -> missing (-3), 10 -> 1, 11 -> 0 copies of the first .bim allele
 static const double lut[4] = {2.0, -3.0, 1.0, 0.0};
 
-S2Common::S2Common(Run& r_, const S2Part& part_) : r(r_), p(r_.p), part(part_), N(r_.N), P(r_.P), C(r_.C) {
-  for (int64_t i = 0; i < N; ++i) if (r.ain[i]) an.push_back(i);
-  n = (int64_t)an.size();
+S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p), part(part_), N(r_.N), P(r_.P), C(r_.C) {
   has_missing.assign(n, 0);
   for (int64_t k = 0; k < n; ++k)
     for (int q = 0; q < P; ++q)
@@ -31,15 +29,6 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : r(r_), p(r_.p), part(part_), 
   multi = part.nparts > 1;                              // parts write plain part files; run_step2_all concatenates (and compresses) them
   for (size_t j = 0; j < r.snp_chrom.size(); ++j) chr_snps[r.snp_chrom[j]].push_back((int64_t)j);
   for (auto& kv : chr_snps) total_blocks += (int)((kv.second.size() + p.bsize - 1) / p.bsize);
-  file_idx.assign(n, 0);
-  int64_t kept = 0, k = 0;
-  for (int64_t i = 0; i < r.n_file && k < n; ++i) {
-    if (r.ind_ignore[i]) continue;
-    if (kept == an[k]) file_idx[k++] = i;
-    ++kept;
-  }
-  identity = n == r.n_file;
-  for (int64_t k = 0; identity && k < n; ++k) identity = file_idx[k] == k;
   nthreads = p.threads > 0 ? p.threads : std::max(1, usable_cpus() - 1);   // Regenie.cpp:1104-1106
   nthreads = std::max(1, std::min(nthreads, 64) / part.nparts);
   // host threads of the BGEN read-ahead: inflate is the bound of this input (about 10 ms per 1.5 MB block and thread with zlib), so it takes

@@ -28,8 +28,44 @@ struct S2Env {
   double bgen_host_share = getenv("RG_S2_BGEN_HOST_SHARE") ? std::min(0.9, std::max(0.0, atof(getenv("RG_S2_BGEN_HOST_SHARE")))) : 0.0;
 };
 
+// The analysed samples of a run: sample k of the analysis (the rows handed to the device) is kept sample an[k] and sample file_idx[k] of the
+// genotype file.
+struct SampleMap {
+  explicit SampleMap(const Run& r) {
+    for (int64_t i = 0; i < r.N; ++i) if (r.ain[i]) an.push_back(i);
+    n = (int64_t)an.size();
+    file_idx.assign(n, 0);
+    int64_t kept = 0, k = 0;
+    for (int64_t i = 0; i < r.n_file && k < n; ++i) {
+      if (r.ind_ignore[i]) continue;
+      if (kept == an[k]) file_idx[k++] = i;
+      ++kept;
+    }
+    identity = n == r.n_file;
+    for (int64_t k = 0; identity && k < n; ++k) identity = file_idx[k] == k;
+  }
+  std::vector<int64_t> an;                      // analysed samples among the kept ones, file order
+  int64_t n = 0;
+  std::vector<int64_t> file_idx;                // file index of every analysed sample
+  bool identity = false;                        // every sample of the file is analysed, in file order
+};
+
+// A dosage as the exact integer the device takes (uint16 rows, 0xFFFF = missing); DOSAGE_NOT_INTEGRAL: the file's value is no such integer.
+constexpr unsigned DOSAGE_NOT_INTEGRAL = 0x10000u;
+// 8-bit .bgen probabilities (b0, b1) in units of 1 / 255: G * 255 = prob1 + 2 prob0, or with --ref-first prob1 + 2 max(1 - prob0 - prob1, 0)
+// (Geno.cpp:2286-2290).  Above 510 (prob0 + prob1 > 1 in the file) it is no dosage in [0, 2]; the value is returned as it is.
+inline unsigned bgen_dosage_255(unsigned b0, unsigned b1, bool ref_first) { return ref_first ? b1 + 2u * (b0 + b1 < 255u ? 255u - b0 - b1 : 0u) : b1 + 2u * b0; }
+inline bool bgen_dosage_integral(unsigned q) { return q <= 510u; }
+// a .pgen dosage in units of 1 / 16384; -3 is the missing value
+inline unsigned pgen_dosage_16384(double g) {
+  if (g == -3.0) return 0xFFFFu;
+  const double v = g * 16384.0, rv = std::nearbyint(v);
+  if (std::fabs(v - rv) > 1e-6 || rv < 0 || rv > 2.0 * 16384.0) return DOSAGE_NOT_INTEGRAL;
+  return (unsigned)rv;
+}
+
 // The run-wide facts of a part, built once and only read afterwards (by the workers of the read-ahead too).
-struct S2Common {
+struct S2Common : SampleMap {
   S2Common(Run& r, const S2Part& part);
   Run& r;
   const Params& p;
@@ -37,14 +73,10 @@ struct S2Common {
   const S2Env env;
   const int64_t N;
   const int P, C;
-  std::vector<int64_t> an;                      // analysed samples (rows handed to the device), file order
-  int64_t n = 0;
   bool any_missing = false;                     // filters->has_missing: a sample masked for at least one trait
   std::vector<uint8_t> has_missing;
   std::vector<double> Xc, Yc;                   // compact, sample-fastest copies for the C ABI
   std::vector<uint8_t> Mc;
-  std::vector<int64_t> file_idx;                // file index of every analysed sample
-  bool identity = false;                        // every sample of the file is analysed, in file order
   std::map<int, std::vector<int64_t>> chr_snps; // blocks per chromosome (set_blocks_for_testing: ceil(n_chr / bsize))
   int total_blocks = 0;
   bool glm, firth, spa, correct, per_trait, show_info, multi, fast_bgen;

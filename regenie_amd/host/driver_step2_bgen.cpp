@@ -243,10 +243,10 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
         if (rf) {     // G = prob1 + 2 prob2, prob2 = max(1 - prob0 - prob1, 0) (Geno.cpp:2286-2290)
           const double p2 = std::max(1.0 - p0 - p1, 0.0);
           v = p1 + 2.0 * p2; e = (4.0 * p2 + p1) - v * v;
-          qi = b1 + 2u * (b0 + b1 < 255u ? 255u - b0 - b1 : 0u);
+          qi = bgen_dosage_255(b0, b1, true);
         } else {
           v = p1 + 2.0 * p0; e = (4.0 * p0 + p1) - v * v;
-          qi = b1 + 2u * b0;
+          qi = bgen_dosage_255(b0, b1, false);
         }
         worst = std::max(worst, qi);
         q16[k] = (uint16_t)qi;
@@ -254,7 +254,7 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
         if (per_trait && has_missing[k]) subtract_masked(Mc, n, P, k, v, e, af_t, ns_t, info_t);
       }
       for (int64_t k = n; k < ld16; ++k) q16[k] = 0;
-      if (worst > 510u) d.host_bad = 1;          // prob0 + prob1 > 1 in the file: not a dosage in [0, 2], the general route reports what the reference would
+      if (!bgen_dosage_integral(worst)) d.host_bad = 1;          // prob0 + prob1 > 1 in the file: not a dosage in [0, 2], the general route reports what the reference would
       d.total[j] = tot; d.ns1[j] = ns; d.info_num[j] = inf;
       d.ignored[j] = below_min_mac(tot, (double)ns, min_mac) ? 1 : 0;
       auto t2 = std::chrono::steady_clock::now();

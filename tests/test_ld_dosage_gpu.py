@@ -131,6 +131,58 @@ def test_cov_and_corr_against_longdouble_restatement(scale, C):
     assert np.array_equal(r2, lr.quantise(cor)[0])
 
 
+TILE_MISS = {"none": (), "middle": (1,), "outer_two": (0, 2), "all": (0, 1, 2)}
+
+
+@pytest.mark.parametrize("which", list(TILE_MISS))
+def test_three_row_tiles_with_and_without_missing_values(which):
+    """tests/test_ld_gpu.py::test_three_row_tiles_with_and_without_missing_calls for integer dosages of scale 255: 257 rows are row tiles
+    of 128, 128 and 1 (a panel each), 65 samples are two K-steps, the tiles named by `which` hold about 10 % missing values; dosages
+    uniform on [0, 510] have a mean near 1, so a B or D tile that is skipped wrongly moves entries by a tenth of their size."""
+    from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix
+    rng = np.random.default_rng(258)
+    n, C, scale, sizes = 65, 2, 255, [128, 128, 1]
+    R = sum(sizes)
+    M = R + 1
+    order = rng.permutation(M)                    # shuffled column order, one forced column
+    forced, filled = order[:1], order[1:]
+    X = _basis(rng, n, C)
+    panels = []
+    for t, bs in enumerate(sizes):
+        G = _dosages(rng, bs, n, scale, 0.1 if t in TILE_MISS[which] else 0.0)
+        if t in TILE_MISS[which]:
+            G[0, 3] = dr.MISSING
+        panels.append(G)
+    Gfull = np.zeros((n, M), dtype=np.uint16)
+    with LDMatrix(n, C, M) as ld:
+        ld.set_basis(X.T)
+        ld.force_columns(forced)
+        starts, c0 = [], 0
+        for k, G in enumerate(panels):
+            cols = filled[c0:c0 + len(G)]
+            ld.append_int(_device(G) if k == 1 else G, cols, scale)
+            Gfull[:, cols] = G.T
+            starts.append(c0)
+            c0 += len(G)
+        _check_pairs(ld, panels, starts, (which,))
+        _check_pairs(ld, [np.concatenate(panels)], [0], (which, "all rows"))      # all rows against themselves: 3 x 3 tiles
+        cov = ld.finish(COV_F64)
+        cor = ld.finish(CORR_F64)
+        r2 = ld.finish(R2_U16)
+    ref_cov = dr.ld_cov(Gfull, scale, X, np.longdouble)
+    ref_cor = dr.corr_of(ref_cov, np.longdouble)
+    np_cov = dr.ld_cov(Gfull, scale, X)
+    d_np_cov, d_lib_cov = _rel_dist(np_cov, ref_cov), _rel_dist(cov, ref_cov)
+    d_np_cor = float(np.max(np.abs(dr.corr_of(np_cov) - ref_cor)))
+    d_lib_cor = float(np.max(np.abs(cor - ref_cor)))
+    print("%s covariance: numpy fp64 %.3e, library %.3e from longdouble; correlation: numpy %.3e, library %.3e" % (which, d_np_cov, d_lib_cov, d_np_cor, d_lib_cor))
+    assert d_lib_cov <= 4 * d_np_cov, (d_lib_cov, d_np_cov)
+    assert d_lib_cor <= 4 * d_np_cor, (d_lib_cor, d_np_cor)
+    assert np.array_equal(cov, cov.T) and np.array_equal(cor, cor.T)
+    assert np.all(cov[forced][:, filled] == 0) and np.all(cor[forced][:, filled] == 0)
+    assert np.array_equal(r2, lr.quantise(cor)[0])
+
+
 @pytest.mark.parametrize("scale", [16384, 255])
 def test_hard_calls_as_dosages_match_the_2bit_path(scale):
     """R2_U16 identical and the covariance within rtol 1e-13 of the 2-bit path's, entry by entry -- at scale 16384.  An entry is a

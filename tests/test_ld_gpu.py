@@ -105,6 +105,65 @@ def test_cov_and_corr_against_longdouble_restatement(C):
     assert np.array_equal(r2, lr.quantise(cor)[0])
 
 
+TILE_MISS = {"none": (), "middle": (1,), "outer_two": (0, 2), "all": (0, 1, 2)}
+
+
+@pytest.mark.parametrize("which", list(TILE_MISS))
+def test_three_row_tiles_with_and_without_missing_calls(which):
+    """The smallest shape at which the Gram kernel takes every branch of its four sums: 257 rows are row tiles of 128, 128 and 1 (appended
+    as three panels, so a panel is a tile), 65 samples are two K-steps, and the tiles named by `which` hold missing calls (about 10 %,
+    allele frequencies of 0.2 to 0.5: a B or D tile that is skipped wrongly, or computed from the wrong tile, moves entries by a tenth
+    of their size).  The sums of panel pairs and of the whole matrix against itself are the exact integer products; covariance and
+    correlation obey the rule of test_cov_and_corr_against_longdouble_restatement."""
+    from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix, pack_bed_rows
+    rng = np.random.default_rng(257)
+    n, C, sizes = 65, 2, [128, 128, 1]
+    R = sum(sizes)
+    M = R + 1
+    order = rng.permutation(M)                    # shuffled column order, one forced column
+    forced, filled = order[:1], order[1:]
+    X = _basis(rng, n, C)
+    panels = []
+    for t, bs in enumerate(sizes):
+        G = rng.binomial(2, rng.uniform(0.2, 0.5, size=bs)[:, None], size=(bs, n)).astype(np.float32)
+        if t in TILE_MISS[which]:
+            G[rng.random(G.shape) < 0.1] = np.nan
+            G[0, 3] = np.nan
+        panels.append(G)
+    Gfull = np.zeros((n, M))
+    with LDMatrix(n, C, M) as ld:
+        ld.set_basis(X.T)
+        ld.force_columns(forced)
+        starts, c0 = [], 0
+        for G in panels:
+            cols = filled[c0:c0 + len(G)]
+            ld.append(pack_bed_rows(G), cols)
+            Gfull[:, cols] = G.T
+            starts.append(c0)
+            c0 += len(G)
+        ints = [_ints(G, False) for G in panels]
+        ints.append(tuple(np.concatenate(x) for x in zip(*ints)))      # all rows against themselves: 3 x 3 tiles
+        for a, b in [(0, 0), (0, 1), (1, 1), (1, 2), (2, 2), (2, 0), (3, 3)]:
+            (ga, ma), (gb, mb) = ints[a], ints[b]
+            got = ld.pair_sums(starts[a % 3], len(ga), starts[b % 3], len(gb))
+            for key, want in (("A", ga @ gb.T), ("B", ga @ mb.T), ("Bt", ma @ gb.T), ("D", ma @ mb.T)):
+                assert np.array_equal(got[key], want), (which, a, b, key)
+        cov = ld.finish(COV_F64)
+        cor = ld.finish(CORR_F64)
+        r2 = ld.finish(R2_U16)
+    ref_cov = lr.ld_cov(Gfull, X, np.longdouble)
+    ref_cor = lr.ld_corr(Gfull, X, np.longdouble)
+    d_np_cov, d_lib_cov = _rel_dist(lr.ld_cov(Gfull, X), ref_cov), _rel_dist(cov, ref_cov)
+    d_np_cor = float(np.max(np.abs(lr.ld_corr(Gfull, X) - ref_cor)))
+    d_lib_cor = float(np.max(np.abs(cor - ref_cor)))
+    print("%s covariance: numpy fp64 %.3e, library %.3e from longdouble; correlation: numpy %.3e, library %.3e" % (which, d_np_cov, d_lib_cov, d_np_cor, d_lib_cor))
+    assert d_lib_cov <= 4 * d_np_cov, (d_lib_cov, d_np_cov)
+    assert d_lib_cor <= 4 * d_np_cor, (d_lib_cor, d_np_cor)
+    assert np.array_equal(cov, cov.T) and np.array_equal(cor, cor.T)
+    assert np.all(cov[forced][:, filled] == 0) and np.all(cor[forced][:, filled] == 0)
+    assert np.array_equal(r2, lr.quantise(cor)[0])
+
+
 def test_size_run_200k_by_4096():
     """n = 200,000, M = 4,096: a row store of 200 MB, 32 tile rows, int32 sums up to 8e5; 64 sampled rows against the restatement."""
     import torch

@@ -69,7 +69,7 @@ int rg_s2_qt_block(rg_s2_ctx* ctx, const double* G, int64_t ldg, int32_t bs, int
  * compute_score_qt (Step2_Models.cpp:402-413: no residualisation, scale_fac = 1, per-trait denominators with the reference's
  * "X'X = I for every trait" approximation) and the others down the dense branch (exact mask_p^T r^2) -- the two are the same
  * number when mask == 1 everywhere, and differ when phenotypes differ in their missing values (then C * P extra contraction
- * columns are carried; at most 4096 columns in all).  The contractions run on the i8 matrix cores with exact integer sums
+ * columns are carried; 4,288 columns in all at 64 covariates and 64 phenotypes).  The contractions run on the i8 matrix cores with exact integer sums
  * (csrc/step2_qt.hip); the genotypes are read at 2 bits each.  rows: host pointer, or device when rows_on_device. */
 int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip,
                           double numtol, const rg_s2_qt_out* out);

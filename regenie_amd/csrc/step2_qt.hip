@@ -635,6 +635,7 @@ struct PackedFinal {
   double zeros_min;        // ... or (>= 0, the .pgen form) when its observed zeros number >= zeros_min
   double *stats, *bhat, *scale_fac, *mean, *total_p;
   int32_t *nobs, *ignored, *nobs_p;
+  int32_t* recheck;        // [bs] or null: 1 for a dense variant whose masked denominators below are ill-conditioned (rg_s2_qt_block_packed)
 };
 
 // thread = (variant, phenotype): the statistic from the contractions and the counts (formulas at the top of the file)
@@ -721,7 +722,12 @@ __global__ void k_s2_packed_final(PackedFinal a) {
   a.bhat[(int64_t)j * P + p] = ign ? NAN : z * a.scf_sv[p] / sd;
   a.total_p[(int64_t)j * P + p] = tot;
   a.nobs_p[(int64_t)j * P + p] = (int32_t)nearbyint(nobs_p);
-  if (p == 0) { a.scale_fac[j] = sf; a.mean[j] = mu; a.nobs[j] = (int32_t)nobs; a.ignored[j] = ign ? 1 : 0; }
+  if (p == 0) {
+    a.scale_fac[j] = sf; a.mean[j] = mu; a.nobs[j] = (int32_t)nobs; a.ignored[j] = ign ? 1 : 0;
+    // modes 1 and 3 form mask_p^T r^2 of a dense variant from three sums of the size of |g~|^2: a variant that lies almost in the span of X
+    // (|r|^2 below 1 / 64 of |g~|^2: a tested variant in strong LD with a conditioning one) loses the digits the ratio takes away
+    if (a.recheck) a.recheck[j] = ((a.masked == 1 || a.masked == 3) && !sparse && !ign && ss < (sq_all + nm * mu * mu) * (1.0 / 64.0)) ? 1 : 0;
+  }
 }
 
 // ---- integer dosages (rg_s2_qt_block_int) -----------------------------------------------------------------------------------------
@@ -1021,7 +1027,9 @@ int ensure_planes(rg_s2_ctx* ctx, bool want_mask_cols) {
     const bool wide = mask_cols && !compact;      // the x_c mask_p / mask_p columns are part of the planes
     const int cv1 = !wide ? C + P : C + P + C * P;
     const int cm0 = !wide ? cv1 : (cv1 + 15) / 16 * 16, cvt = !wide ? cv1 : cm0 + P;
-    if (cvt > 4096) return fail(ctx, RG_S2_ERR_ARG, "covariates x phenotypes with differing missing values > 4096 columns");
+    // (at most RG_S2_MAX_COV + RG_S2_MAX_PHENO * (RG_S2_MAX_COV + 2) = 4,288 columns: every basis and phenotype count rg_s2_create accepts)
+    if (cvt > RG_S2_MAX_COV + RG_S2_MAX_PHENO * (RG_S2_MAX_COV + 2))
+      return fail(ctx, RG_S2_ERR_ARG, "covariates x phenotypes with differing missing values > 4288 columns");
     const int ngrp = (cvt + 15) / 16;
     ctx->Np = (n + 128 * RG_MAX_SEG - 1) / (128 * RG_MAX_SEG) * (128 * RG_MAX_SEG);   // 32 pieces of a multiple of 128 samples
     for (void** q : {(void**)&ctx->dV, (void**)&ctx->dvd, (void**)&ctx->dvsc, (void**)&ctx->dYtX, (void**)&ctx->dQ, (void**)&ctx->dMsum})
@@ -1378,7 +1386,7 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
     if ((rc = ensure_p(ctx, Q_L, (size_t)bs * P * ((2 * Cc + 1) * sizeof(double) + 4 * sizeof(int32_t))))) return rc;       // Lc [bs][2][P][Cc] | Lq [bs][P] | call counts [bs][P][4]
   }
   if ((rc = ensure_p(ctx, Q_A, (size_t)bs * 2 * (Cvt + CvB) * sizeof(double)))) return rc;
-  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 2 * sizeof(int32_t))))) return rc;   // scale_fac | mean | vstat[4] | nobs | ignored
+  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 3 * sizeof(int32_t))))) return rc;   // scale_fac | mean | vstat[4] | nobs | ignored | recheck
   if ((rc = ensure_p(ctx, Q_STAT, (size_t)bs * P * (3 * sizeof(double) + sizeof(int32_t))))) return rc;  // stats | bhat | total_p | nobs_p
   uint8_t* pk = (uint8_t*)ctx->pbuf[Q_PK];
   int32_t* cnt = (int32_t*)ctx->pbuf[Q_CNT];
@@ -1393,6 +1401,7 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   double* vstat = mu + bs;
   int32_t* nobs = (int32_t*)(vstat + (size_t)bs * 4);
   int32_t* ign = nobs + bs;
+  int32_t* recheck = ign + bs;
   double* stats = (double*)ctx->pbuf[Q_STAT];
   double* bhat = stats + (size_t)bs * P;
   double* total_p = bhat + (size_t)bs * P;
@@ -1457,6 +1466,7 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   fa.n = n; fa.numtol = numtol; fa.nz_max = (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * (1.0 - ctx->rule_thr);
   fa.zeros_min = ctx->rule_zero_count ? (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * ctx->rule_thr : -1.0;
   fa.stats = stats; fa.bhat = bhat; fa.scale_fac = sf; fa.mean = mu; fa.total_p = total_p; fa.nobs = nobs; fa.ignored = ign; fa.nobs_p = nobs_p;
+  fa.recheck = masked ? recheck : nullptr;
   hipLaunchKernelGGL(k_s2_packed_final, dim3((bs * P + 255) / 256), dim3(256), 0, ctx->st, fa);
   S2_HIP(hipEventRecord(ctx->e1, ctx->st));
   S2_HIP(hipGetLastError());
@@ -1468,10 +1478,39 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   if (out->ignored) S2_HIP(hipMemcpyAsync(out->ignored, ign, sizeof(int32_t) * bs, hipMemcpyDeviceToHost, ctx->st));
   if (out->total_p) S2_HIP(hipMemcpyAsync(out->total_p, total_p, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
   if (out->n_obs_p) S2_HIP(hipMemcpyAsync(out->n_obs_p, nobs_p, sizeof(int32_t) * bs * P, hipMemcpyDeviceToHost, ctx->st));
+  std::vector<int32_t> h_recheck(masked ? bs : 0);
+  if (masked) S2_HIP(hipMemcpyAsync(h_recheck.data(), recheck, sizeof(int32_t) * bs, hipMemcpyDeviceToHost, ctx->st));
   S2_HIP(hipStreamSynchronize(ctx->st));
   float ms = 0.f;
   S2_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
   ctx->last_ms = ms;
+  // The flagged variants (rare: a dense variant almost in the span of X) once more through rg_s2_qt_block, which forms the residual
+  // g~ - X beta itself and sums mask_p r^2 over it: their staged rows (flip applied) come back, are decoded on the host and go in as fp64.
+  std::vector<int32_t> redo;
+  for (int j = 0; j < (int)h_recheck.size(); ++j) if (h_recheck[j]) redo.push_back(j);
+  if (!redo.empty() && (out->stats || out->bhat || out->scale_fac)) {
+    const size_t nf = redo.size();
+    std::vector<uint8_t> hrow((size_t)nbytes);
+    std::vector<double> hg(nf * (size_t)n), t_stats(nf * P), t_bhat(nf * P), t_sf(nf);
+    std::vector<int32_t> t_ign(nf);
+    for (size_t k = 0; k < nf; ++k) {
+      S2_HIP(hipMemcpy(hrow.data(), pk + (int64_t)redo[k] * ldp, (size_t)nbytes, hipMemcpyDeviceToHost));
+      static const double val[4] = {2.0, NAN, 1.0, 0.0};      // .bed codes 00, 01 (missing), 10, 11
+      for (int64_t i = 0; i < n; ++i) hg[k * (size_t)n + i] = val[(hrow[i >> 2] >> (2 * (i & 3))) & 3];
+    }
+    rg_s2_qt_out o;
+    memset(&o, 0, sizeof(o));
+    o.stats = t_stats.data(); o.bhat = t_bhat.data(); o.scale_fac = t_sf.data(); o.ignored = t_ign.data();
+    if ((rc = rg_s2_qt_block(ctx, hg.data(), n, (int32_t)nf, 0, numtol, &o))) return rc;
+    ctx->last_ms += ms;
+    for (size_t k = 0; k < nf; ++k) {
+      if (t_ign[k]) continue;
+      const size_t j = (size_t)redo[k];
+      if (out->stats) memcpy(out->stats + j * P, t_stats.data() + k * P, sizeof(double) * P);
+      if (out->bhat) memcpy(out->bhat + j * P, t_bhat.data() + k * P, sizeof(double) * P);
+      if (out->scale_fac) out->scale_fac[j] = t_sf[k];
+    }
+  }
   return RG_S2_OK;
 }
 
@@ -1567,6 +1606,7 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   fa.n = n; fa.numtol = numtol; fa.nz_max = (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * (1.0 - ctx->rule_thr);
   fa.zeros_min = ctx->rule_zero_count ? (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * ctx->rule_thr : -1.0;
   fa.stats = stats; fa.bhat = bhat; fa.scale_fac = sf; fa.mean = mu; fa.total_p = total_p; fa.nobs = nobs; fa.ignored = ign; fa.nobs_p = nobs_p;
+  fa.recheck = nullptr;      // (mode 2 subtracts the masked samples' own residual sum)
   hipLaunchKernelGGL(k_s2_packed_final, dim3((bs * P + 255) / 256), dim3(256), 0, ctx->st, fa);
   S2_HIP(hipEventRecord(ctx->e1, ctx->st));
   S2_HIP(hipGetLastError());

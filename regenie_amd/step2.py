@@ -140,16 +140,25 @@ class Step2QT:
         self._check(self.lib.rg_s2_qt_block_packed(self.h, ptr, ld, bs, on_device, 1 if flip else 0, float(numtol), C.byref(out)))
         return self._finish(res)
 
-    def score_block_int(self, G: np.ndarray, scale: int, numtol: float = NUMTOL) -> dict:
-        """Integer dosages: G [bs][n] uint16 in units of 1 / scale (255 for 8-bit .bgen probabilities, 16384 for .pgen), 0xFFFF = missing."""
-        G = np.ascontiguousarray(G, dtype=np.uint16)
-        if G.ndim != 2 or G.shape[1] != self.n:
-            raise ValueError("score_block_int: G must be [bs][n]")
-        bs = G.shape[0]
+    def score_block_int(self, G, scale: int, numtol: float = NUMTOL) -> dict:
+        """Integer dosages: G [bs][n] uint16 in units of 1 / scale (255 for 8-bit .bgen probabilities, 16384 for .pgen), 0xFFFF = missing
+        (numpy, or a CUDA torch tensor of 2-byte elements read in place; its row pitch may exceed n)."""
+        on_device = 0
+        if isinstance(G, np.ndarray):
+            G = np.ascontiguousarray(G, dtype=np.uint16)
+            if G.ndim != 2 or G.shape[1] != self.n:
+                raise ValueError("score_block_int: G must be [bs][n]")
+            bs, ld, ptr = G.shape[0], G.shape[1], G.ctypes.data
+        else:
+            if not (G.is_cuda and G.element_size() == 2 and G.dim() == 2 and G.stride(1) == 1 and G.shape[1] == self.n):
+                raise ValueError("score_block_int: device G must be a 2-d [bs][n] CUDA tensor of 2-byte elements with unit sample stride")
+            bs, ld, ptr, on_device = G.shape[0], G.stride(0), G.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(G.device).synchronize()   # the library runs on its own stream
         res = {"stats": np.empty((bs, self.P)), "bhat": np.empty((bs, self.P)), "scale_fac": np.empty(bs),
                "mean": np.empty(bs), "n_obs": np.empty(bs, np.int32), "ignored": np.empty(bs, np.int32)}
         out = _QtOut(*[res[k].ctypes.data for k in ("stats", "bhat", "scale_fac", "mean", "n_obs", "ignored")])
-        self._check(self.lib.rg_s2_qt_block_int(self.h, G.ctypes.data, G.shape[1], bs, 0, int(scale), float(numtol), C.byref(out)))
+        self._check(self.lib.rg_s2_qt_block_int(self.h, ptr, ld, bs, on_device, int(scale), float(numtol), C.byref(out)))
         return self._finish(res)
 
     # ---- the contraction primitive (rg_s2_set_columns / rg_s2_contract_packed) ------------------------------------------------

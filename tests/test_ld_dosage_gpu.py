@@ -90,15 +90,16 @@ def _rel_dist(a, ref):
     return float(np.max(np.abs(np.asarray(a, dtype=np.longdouble) - ref) / (d[:, None] * d[None, :])))
 
 
-@pytest.mark.parametrize("C", [1, 12])
+@pytest.mark.parametrize("C", [1, 12, 33, 64])
 @pytest.mark.parametrize("scale", [255, 16384])
 def test_cov_and_corr_against_longdouble_restatement(scale, C):
     """The rule of tests/test_ld_gpu.py: the library may be at most 4 x as far from the longdouble restatement as numpy's float64
-    restatement is (max over entries, relative to sqrt(LD_ii LD_jj)): both round the same fp64 sums, in a different order."""
+    restatement is (max over entries, relative to sqrt(LD_ii LD_jj)): both round the same fp64 sums, in a different order.  C = 33 and
+    64: the basis of a conditional analysis, X^T g from rg_s2_contract_int over three and four column groups."""
     from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix
     rng = np.random.default_rng(500 + scale + C)
-    n, M, nforced = 5000, 600, 7
-    sizes = [256, 200, M - nforced - 456]
+    n, M, nforced = (5000, 600, 7) if C <= 12 else (1031, 263, 7)      # (the longdouble restatement takes two passes over the dosages per basis column)
+    sizes = [256, 200, M - nforced - 456] if C <= 12 else [128, 70, M - nforced - 198]
     order = rng.permutation(M)
     forced, filled = order[:nforced], order[nforced:]
     Gfull = np.zeros((n, M), dtype=np.uint16)
@@ -129,6 +130,27 @@ def test_cov_and_corr_against_longdouble_restatement(scale, C):
     assert np.array_equal(cov, cov.T) and np.array_equal(cor, cor.T)
     assert np.all(cor[forced][:, filled] == 0) and np.allclose(np.diag(cor)[forced], 1.0, rtol=0, atol=1e-15)
     assert np.array_equal(r2, lr.quantise(cor)[0])
+
+
+@pytest.mark.parametrize("scale", [255, 16384])
+def test_columns_that_copy_basis_columns(scale):
+    """tests/test_ld_gpu.py::test_columns_that_copy_basis_columns for integer dosages: two columns of the matrix are the hard calls the
+    analysis conditions on, handed over in units of 1 / scale (C = 33: intercept, 30 covariates, the two variants)."""
+    from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix
+    from tests.test_ld_gpu import _copy_basis, check_copied_columns
+    rng = np.random.default_rng(434 + scale)
+    n, C, M, copies = 2051, 33, 200, np.array([17, 151])
+    G = _dosages(rng, M, n, scale, 0.02)
+    G[copies] = rng.binomial(2, 0.4, size=(2, n)) * scale
+    G[copies[0], rng.random(n) < 0.02] = dr.MISSING
+    Gf = dr.to_float(G.T, scale)
+    X = _copy_basis(rng, n, C, lr.mean_impute(Gf[:, copies]))
+    with LDMatrix(n, C, M) as ld:
+        ld.set_basis(X.T)
+        ld.append_int(G[:130], np.arange(130), scale)
+        ld.append_int(_device(G[130:]), np.arange(130, M), scale)
+        cov, cor, r2 = ld.finish(COV_F64), ld.finish(CORR_F64), ld.finish(R2_U16)
+    check_copied_columns(cov, cor, r2, Gf, X, dr.ld_cov(G.T, scale, X, np.longdouble), dr.ld_cov(G.T, scale, X), copies)
 
 
 TILE_MISS = {"none": (), "middle": (1,), "outer_two": (0, 2), "all": (0, 1, 2)}

@@ -65,14 +65,16 @@ def _rel_dist(a, ref):
     return float(np.max(np.abs(np.asarray(a, dtype=np.longdouble) - ref) / (d[:, None] * d[None, :])))
 
 
-@pytest.mark.parametrize("C", [1, 12])
+@pytest.mark.parametrize("C", [1, 12, 33, 64])
 def test_cov_and_corr_against_longdouble_restatement(C):
     """Tolerance (set by the issue): the library may be at most 4 x as far from the longdouble restatement as numpy's float64
-    restatement is (max over entries, relative to sqrt(LD_ii LD_jj))."""
+    restatement is (max over entries, relative to sqrt(LD_ii LD_jj)).  C = 33 and 64: the basis of a conditional analysis (the
+    projection of k_ld_combine over three groups of 16 columns and one more, and over all of RG_S2_MAX_COV), on a smaller matrix:
+    the longdouble restatement takes one pass over the calls per basis column."""
     from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix, pack_bed_rows
     rng = np.random.default_rng(77 + C)
-    n, M, nforced = 20000, 1500, 7
-    sizes = [600, 500, M - nforced - 1100]
+    n, M, nforced = (20000, 1500, 7) if C <= 12 else (1031, 263, 7)
+    sizes = [600, 500, M - nforced - 1100] if C <= 12 else [100, 90, M - nforced - 190]
     order = rng.permutation(M)                    # scrambled column order
     forced, filled = order[:nforced], order[nforced:]
     Gfull = np.zeros((n, M))
@@ -103,6 +105,66 @@ def test_cov_and_corr_against_longdouble_restatement(C):
     assert np.all(cor[forced][:, filled] == 0) and np.allclose(np.diag(cor)[forced], 1.0, rtol=0, atol=1e-15)
     # the triangle quantised on the device is the quantisation of the library's own correlations, bit for bit
     assert np.array_equal(r2, lr.quantise(cor)[0])
+
+
+def _copy_basis(rng, n, C, imputed):
+    """[1, C - 1 - k normal covariates, the k mean-imputed variants] orthonormalised: the basis of an analysis conditional on them."""
+    return np.linalg.qr(np.column_stack([np.ones(n), rng.normal(size=(n, C - 1 - imputed.shape[1])), imputed]))[0]
+
+
+def check_copied_columns(cov, cor, r2, Gfull, X, ref_cov, np_cov, copies):
+    """Columns `copies` of the matrix are exact copies of basis columns (a variant of the region that the analysis conditions on): their
+    projected variance is rounding noise around zero.  What is asserted is what does not depend on the sign of that noise:
+      - among the OTHER columns the rule of test_cov_and_corr_against_longdouble_restatement;
+      - a copy's row of the covariance is zero up to the rounding of its two terms, |LD_ij| <= 4 n eps |g_i| |g_j| (each of g_i . g_j and
+        (X^T g_i) . (X^T g_j) is a sum of n, resp. C products bounded by |g_i| |g_j|, with the worst-case bound n eps of a length-n sum;
+        the factor 4 covers the two terms and the sums inside X^T g);
+      - print_ld's diagonal rules (tests/ld_dosage_restate.py: corr_of) on the library's own covariance give the library's correlations:
+        finite, unit diagonal -- sqrt(numtol) stands in for a non-positive variance -- and never NaN;
+      - R^2 of a copy with any other column quantises to 0, in the library as in both restatements (the copy-copy pair is noise over noise
+        and is left out), and the device-side quantisation is that of the library's own correlations."""
+    from tests import ld_dosage_restate as dr
+    M = cov.shape[0]
+    others = np.setdiff1d(np.arange(M), copies)
+    sub = np.ix_(others, others)
+    d_np, d_lib = _rel_dist(np_cov[sub], ref_cov[sub]), _rel_dist(cov[sub], ref_cov[sub])
+    ref_cor, np_cor = dr.corr_of(ref_cov, np.longdouble), dr.corr_of(np_cov)
+    d_np_cor, d_lib_cor = float(np.max(np.abs(np_cor[sub] - ref_cor[sub]))), float(np.max(np.abs(cor[sub] - ref_cor[sub])))
+    print("copied columns: diagonal %s (library), %s (numpy); others: covariance numpy %.3e, library %.3e; correlation numpy %.3e, library %.3e"
+          % (np.diag(cov)[copies], np.diag(np_cov)[copies], d_np, d_lib, d_np_cor, d_lib_cor))
+    assert d_lib <= 4 * d_np, (d_lib, d_np)
+    assert d_lib_cor <= 4 * d_np_cor, (d_lib_cor, d_np_cor)
+    norm = np.sqrt((lr.mean_impute(Gfull) ** 2).sum(axis=0))
+    n = Gfull.shape[0]
+    assert (np.abs(cov[copies]) <= 4 * n * np.finfo(np.float64).eps * norm[copies][:, None] * norm[None, :]).all()
+    assert np.isfinite(cov).all() and np.isfinite(cor).all()
+    assert np.array_equal(cov, cov.T) and np.array_equal(cor, cor.T)
+    np.testing.assert_allclose(cor, dr.corr_of(cov), rtol=1e-14, atol=0)
+    np.testing.assert_allclose(np.diag(cor), 1.0, rtol=0, atol=1e-15)
+    iu = np.triu_indices(M, 1)
+    pair_with_other = np.isin(iu[0], copies) ^ np.isin(iu[1], copies)
+    for name, c in (("library", cor), ("numpy", np_cor), ("longdouble", ref_cor)):
+        assert (lr.quantise(c)[0][pair_with_other] == 0).all(), name
+    assert (r2[pair_with_other] == 0).all()
+    assert np.array_equal(r2, lr.quantise(cor)[0])
+
+
+def test_columns_that_copy_basis_columns():
+    """Two columns of the LD matrix are the conditioning variants themselves (C = 33: intercept, 30 covariates, the two variants)."""
+    from regenie_amd.ld import COV_F64, CORR_F64, R2_U16, LDMatrix, pack_bed_rows
+    rng = np.random.default_rng(433)
+    n, C, M, copies = 2051, 33, 200, np.array([17, 151])
+    G = _calls(rng, M, n, 0.02)
+    G[copies] = rng.binomial(2, 0.4, size=(2, n))
+    G[copies[0], rng.random(n) < 0.02] = np.nan
+    Gfull = G.T.astype(np.float64)
+    X = _copy_basis(rng, n, C, lr.mean_impute(Gfull[:, copies]))
+    with LDMatrix(n, C, M) as ld:
+        ld.set_basis(X.T)
+        ld.append(pack_bed_rows(G[:130]), np.arange(130))
+        ld.append(pack_bed_rows(G[130:]), np.arange(130, M))
+        cov, cor, r2 = ld.finish(COV_F64), ld.finish(CORR_F64), ld.finish(R2_U16)
+    check_copied_columns(cov, cor, r2, Gfull, X, lr.ld_cov(Gfull, X, np.longdouble), lr.ld_cov(Gfull, X), copies)
 
 
 TILE_MISS = {"none": (), "middle": (1,), "outer_two": (0, 2), "all": (0, 1, 2)}

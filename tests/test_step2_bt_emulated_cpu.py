@@ -47,9 +47,11 @@ def gpu_tests(emulated, monkeypatch):
     return t
 
 
+@pytest.mark.parametrize("C", [3, 40])
 @pytest.mark.parametrize("route", ["packed", "int"])
-def test_score_and_corrections_on_the_emulated_device(gpu_tests, route):
-    gpu_tests.test_bt_score_and_corrections_against_the_oracle(route)          # the GPU test's own body, at its own size (3,001 samples, 96 pairs x 2 forms x 2 corrections)
+def test_score_and_corrections_on_the_emulated_device(gpu_tests, route, C):
+    # the GPU test's own body, at its own sizes: 3 covariates (3,001 samples, 96 pairs x 2 forms x 2 corrections) and 40 (4,001 samples, 48 pairs; the wide tc[] / stc[] paths)
+    gpu_tests.test_bt_score_and_corrections_against_the_oracle(route, C)
 
 
 @pytest.mark.parametrize("route", ["packed", "int"])

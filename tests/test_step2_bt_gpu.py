@@ -45,10 +45,14 @@ def _nulls(X, off, y, mask):
     return nulls, np.array(fo)
 
 
+@pytest.mark.parametrize("C", [3, 20, 40, 64])
 @pytest.mark.parametrize("route", ["packed", "int"])
-def test_bt_score_and_corrections_against_the_oracle(route):
+def test_bt_score_and_corrections_against_the_oracle(route, C):
+    """C = 3: the block of 48 variants this test has always run.  C = 20, 40, 64: the widths a conditional analysis reaches (every conditioning
+    variant is a column of X) -- the per-thread tc[] and the LDS stc[] of k_bt_firth1 / k_bt_spa and the C x C solves of the score test filled
+    to a third, two thirds and all of RG_S2_MAX_COV -- on 4,001 samples and 24 variants."""
     from regenie_amd.step2 import BT_FIRTH_APPROX, BT_SPA, Step2QT
-    X, off, G, y, mask = _problem(11)
+    X, off, G, y, mask = _problem(11) if C == 3 else _problem(11 + C, n=4001, C=C, bs=24)
     bs, n = G.shape
     P = y.shape[1]
     nulls, fo = _nulls(X, off, y, mask)

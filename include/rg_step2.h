@@ -11,7 +11,7 @@
  *   rg_s2_qt_block_packed  the same for hard calls as they lie in a .bed file, INCLUDING the sparse-genotype branch the
  *                     reference takes per variant (check_sparse_G, Geno.cpp:3165-3177; Step2_Models.cpp:402-413)
  * Not in this slice (the host keeps doing them): reading the LOCO file (blup_read_chr), the MAC / INFO filters, --strict,
- * mse_full, MCC, the p-value and the output lines.  Both entries make check_sparse_G's per-variant choice (rg_s2_set_sparse_rule).
+ * mse_full, the closed-form part of MCC (rg_s2_qt_moments below returns its device sums), the p-value and the output lines.  Both entries make check_sparse_G's per-variant choice (rg_s2_set_sparse_rule).
  *
  * Layout: every matrix is row-major with the SAMPLE index fastest -- G is [bs][ldg], X is [C][n], yres and mask are [P][n];
  * n = samples in the analysis, in the caller's order.  A missing genotype is NaN or any value < 0 (regenie's -3).
@@ -177,7 +177,20 @@ typedef struct rg_s2_bt_corr {
 int rg_s2_bt_correct(rg_s2_ctx* ctx, int32_t kind, int32_t npair, const int32_t* variant, const int32_t* trait, const uint8_t* fast, int32_t firth_se,
                      rg_s2_bt_corr* out);
 
-/* Device time of the kernels of the last rg_s2_qt_block / rg_s2_qt_block_packed call (hipEvents on the library's stream), in ms. */
+/* ---- quantitative traits: the sums of the moment-matched correlation test (`--mcc`; compute_score_qt_mcc, Step2_Models.cpp:237-341) -----------
+ * MCCResults::dkat (MCC.cpp:500-645) needs, per (variant, trait), masked power sums of the genotype vector the score test has built -- Gmat.col(isnp),
+ * Data.cpp:2501-2515: the mean-imputed raw genotype for a variant check_sparse_G calls sparse, residualize_geno's output (g~ - X X^T g~) / scale_fac
+ * otherwise.  rg_s2_qt_moments works on the block LAST scored by rg_s2_qt_block, rg_s2_qt_block_packed or rg_s2_qt_block_int, which stays on the
+ * device (rows handed over as a device pointer are read in place once more: keep them alive), with the verdict, mean, flip and scale_fac THAT call
+ * produced.  For each listed row v (index into the block) and every trait t, sums[(v * P + t) * 7 + ...] =
+ *   [k - 1]  S_k = sum_i mask_t(i) r_v(i)^k, k = 1..6        [6]  sum_i r_v(i) yres_t(i)
+ * in fp64 with a fixed two-stage summation order (no floating-point atomics: two calls return the same bits).  X^T g~ is recomputed from the row.
+ * Rows the score call reported as ignored may be listed; their sums mean nothing.  The moments, the gamma tail and the substitution of LOG10P / SE
+ * are closed form and stay with the caller (regenie_amd/host/driver_models.cpp: mcc_pvalue). */
+typedef struct rg_s2_mcc_out { double* sums; /* [nv][P][7], HOST pointer */ } rg_s2_mcc_out;
+int rg_s2_qt_moments(rg_s2_ctx* ctx, int32_t nv, const int32_t* variant, const rg_s2_mcc_out* out);
+
+/* Device time of the kernels of the last rg_s2_qt_block / rg_s2_qt_block_packed / rg_s2_qt_moments call (hipEvents on the library's stream), in ms. */
 double rg_s2_last_kernel_ms(const rg_s2_ctx* ctx);
 
 #ifdef __cplusplus

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rg_step2.h"
@@ -72,6 +73,19 @@ struct rg_s2_ctx {
   std::string err;
   // ---- binary / count traits behind the ABI (step2_bt.hip): null model per chromosome, the block last scored, correction buffers ----
   struct BtState* bt = nullptr;
+  // ---- the block LAST scored by a quantitative-trait entry, as rg_s2_qt_moments (step2_mcc.hip) reads it: the rows where the entry left them
+  // (or where the caller keeps them: device input is read in place), and the mean / scale_fac / check_sparse_G verdict its final kernel wrote
+  struct LastQt {
+    int kind = 0;               // 0: none (also after any other entry that reuses the staging buffers, and after rg_s2_set_null), 1: fp64 rows (rg_s2_qt_block), 2: staged 2-bit rows, flip applied (_packed), 3: uint16 rows (_int)
+    const void* rows = nullptr;
+    int64_t ld = 0;             // elements (kind 1, 3) or bytes (kind 2) between rows
+    int bs = 0, scale = 1;
+    const double *sf = nullptr, *mu = nullptr;
+    const int32_t* sparse = nullptr;
+    std::vector<std::pair<int32_t, double>> sf_fix;      // rows whose scale_fac the caller was given from a second look (rg_s2_qt_block_packed): applied to sf by rg_s2_qt_moments
+  } last_qt;
+  void* mbuf[4] = {nullptr, nullptr, nullptr, nullptr};      // rg_s2_qt_moments: listed rows, partial sums, b, results
+  size_t mcap[4] = {0, 0, 0, 0};
 };
 
 
@@ -101,3 +115,4 @@ enum { RG_S2_Q_PK = 0, RG_S2_Q_CNT = 1, RG_S2_Q_S = 2, RG_S2_Q_A = 3, RG_S2_Q_VA
 // slot of rg_s2_ctx::buf holding the uint16 dosage rows of the block handed to the integer-dosage entries from the host
 enum { RG_S2_B_G = 0 };
 void rg_s2_bt_free(rg_s2_ctx* ctx);   // step2_bt.hip
+void rg_s2_mcc_free(rg_s2_ctx* ctx);  // step2_mcc.hip

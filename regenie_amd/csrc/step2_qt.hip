@@ -341,7 +341,8 @@ __global__ void k_s2_final(const double* __restrict__ part2, int nchunk, int P, 
                            double zeros_min /* < 0: the non-zero form of the rule */,
                            const double* __restrict__ scf_sv, const int32_t* __restrict__ nobs, const int32_t* __restrict__ nnz,
                            const double* __restrict__ mu, const double* __restrict__ beta, const double* __restrict__ corr /* null: no masked sample */,
-                           double* __restrict__ stats, double* __restrict__ bhat, double* __restrict__ scale_fac, int32_t* __restrict__ ignored) {
+                           double* __restrict__ stats, double* __restrict__ bhat, double* __restrict__ scale_fac, int32_t* __restrict__ ignored,
+                           int32_t* __restrict__ sparse_out /* the verdict, kept for rg_s2_qt_moments */) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= bs * P) return;
   const int j = t / P, p = t % P, Q2 = 1 + 2 * P;
@@ -371,7 +372,7 @@ __global__ void k_s2_final(const double* __restrict__ part2, int nchunk, int P, 
   const double z = num / sd;
   stats[(int64_t)j * P + p] = ign ? NAN : z;
   bhat[(int64_t)j * P + p] = ign ? NAN : z * scf_sv[p] / sd;
-  if (p == 0) { scale_fac[j] = sf; ignored[j] = ign ? 1 : 0; }
+  if (p == 0) { scale_fac[j] = sf; ignored[j] = ign ? 1 : 0; sparse_out[j] = sparse ? 1 : 0; }
 }
 
 // ---- hard-call route ---------------------------------------------------------------------------------------------------------
@@ -636,6 +637,7 @@ struct PackedFinal {
   double *stats, *bhat, *scale_fac, *mean, *total_p;
   int32_t *nobs, *ignored, *nobs_p;
   int32_t* recheck;        // [bs] or null: 1 for a dense variant whose masked denominators below are ill-conditioned (rg_s2_qt_block_packed)
+  int32_t* sparse_out;     // [bs]: the verdict, kept for rg_s2_qt_moments
 };
 
 // thread = (variant, phenotype): the statistic from the contractions and the counts (formulas at the top of the file)
@@ -723,7 +725,7 @@ __global__ void k_s2_packed_final(PackedFinal a) {
   a.total_p[(int64_t)j * P + p] = tot;
   a.nobs_p[(int64_t)j * P + p] = (int32_t)nearbyint(nobs_p);
   if (p == 0) {
-    a.scale_fac[j] = sf; a.mean[j] = mu; a.nobs[j] = (int32_t)nobs; a.ignored[j] = ign ? 1 : 0;
+    a.scale_fac[j] = sf; a.mean[j] = mu; a.nobs[j] = (int32_t)nobs; a.ignored[j] = ign ? 1 : 0; a.sparse_out[j] = sparse ? 1 : 0;
     // modes 1 and 3 form mask_p^T r^2 of a dense variant from three sums of the size of |g~|^2: a variant that lies almost in the span of X
     // (|r|^2 below 1 / 64 of |g~|^2: a tested variant in strong LD with a conditioning one) loses the digits the ratio takes away
     if (a.recheck) a.recheck[j] = ((a.masked == 1 || a.masked == 3) && !sparse && !ign && ss < (sq_all + nm * mu * mu) * (1.0 / 64.0)) ? 1 : 0;
@@ -1235,6 +1237,7 @@ void rg_s2_destroy(rg_s2_ctx* ctx) {
     if (ctx->dM) (void)hipFree(ctx->dM);
     if (ctx->dscf) (void)hipFree(ctx->dscf);
     rg_s2_bt_free(ctx);
+    rg_s2_mcc_free(ctx);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
     if (ctx->e1) (void)hipEventDestroy(ctx->e1);
     (void)hipStreamDestroy(ctx->st);
@@ -1248,6 +1251,7 @@ int rg_s2_set_null(rg_s2_ctx* ctx, const double* X, const double* yres, const ui
   if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_null: context was not created");
   if (!X || !yres || !mask || !scf_sv) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_null: null argument");
   S2_HIP(hipSetDevice(ctx->dev));
+  ctx->last_qt.kind = 0;      // a scored block belongs to the null model it was scored under
   S2_HIP(hipMemcpyAsync(ctx->dX, X, sizeof(double) * ctx->n * ctx->C, hipMemcpyHostToDevice, ctx->st));
   S2_HIP(hipMemcpyAsync(ctx->dY, yres, sizeof(double) * ctx->n * ctx->P, hipMemcpyHostToDevice, ctx->st));
   S2_HIP(hipMemcpyAsync(ctx->dM, mask, (size_t)ctx->n * ctx->P, hipMemcpyHostToDevice, ctx->st));
@@ -1298,7 +1302,7 @@ int rg_s2_qt_block(rg_s2_ctx* ctx, const double* G, int64_t ldg, int32_t bs, int
   if ((rc = ensure(ctx, B_PART, part_elems * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, B_BETA, (size_t)bs * RG_S2_MAX_COV * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, B_VAR, (size_t)bs * 2 * sizeof(double)))) return rc;       // mu | scale_fac
-  if ((rc = ensure(ctx, B_NOBS, (size_t)bs * 3 * sizeof(int32_t)))) return rc;     // nobs | ignored | nnz
+  if ((rc = ensure(ctx, B_NOBS, (size_t)bs * 4 * sizeof(int32_t)))) return rc;     // nobs | ignored | nnz | sparse
   const bool masked = !ctx->complete;
   if (masked && (rc = ensure(ctx, B_CORR, (size_t)bs * P * (C + 1) * sizeof(double)))) return rc;
   if (masked && (rc = ensure_lists(ctx))) return rc;
@@ -1319,6 +1323,7 @@ int rg_s2_qt_block(rg_s2_ctx* ctx, const double* G, int64_t ldg, int32_t bs, int
   int32_t* nobs = (int32_t*)ctx->buf[B_NOBS];
   int32_t* ign = nobs + bs;
   int32_t* nnz = ign + bs;
+  int32_t* sparse = nnz + bs;
   double* stats = (double*)ctx->buf[B_STAT];
   double* bhat = stats + (size_t)bs * P;
   double* corr = masked ? (double*)ctx->buf[B_CORR] : nullptr;
@@ -1339,7 +1344,10 @@ int rg_s2_qt_block(rg_s2_ctx* ctx, const double* G, int64_t ldg, int32_t bs, int
   hipLaunchKernelGGL(k_s2_final, dim3((bs * P + 255) / 256), dim3(256), 0, ctx->st, part, nchunk, P, C, bs, n, numtol,
                      (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * (1.0 - ctx->rule_thr),
                      ctx->rule_zero_count ? (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * ctx->rule_thr : -1.0, ctx->dscf, nobs, nnz, mu, beta, corr, stats,
-                     bhat, sf, ign);
+                     bhat, sf, ign, sparse);
+  ctx->last_qt.sf_fix.clear();
+  ctx->last_qt.kind = 1; ctx->last_qt.rows = dG; ctx->last_qt.ld = ld; ctx->last_qt.bs = bs; ctx->last_qt.scale = 1;
+  ctx->last_qt.sf = sf; ctx->last_qt.mu = mu; ctx->last_qt.sparse = sparse;
   S2_HIP(hipEventRecord(ctx->e1, ctx->st));
   S2_HIP(hipGetLastError());
   if (out->stats) S2_HIP(hipMemcpyAsync(out->stats, stats, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
@@ -1386,7 +1394,7 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
     if ((rc = ensure_p(ctx, Q_L, (size_t)bs * P * ((2 * Cc + 1) * sizeof(double) + 4 * sizeof(int32_t))))) return rc;       // Lc [bs][2][P][Cc] | Lq [bs][P] | call counts [bs][P][4]
   }
   if ((rc = ensure_p(ctx, Q_A, (size_t)bs * 2 * (Cvt + CvB) * sizeof(double)))) return rc;
-  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 3 * sizeof(int32_t))))) return rc;   // scale_fac | mean | vstat[4] | nobs | ignored | recheck
+  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 4 * sizeof(int32_t))))) return rc;   // scale_fac | mean | vstat[4] | nobs | ignored | recheck | sparse
   if ((rc = ensure_p(ctx, Q_STAT, (size_t)bs * P * (3 * sizeof(double) + sizeof(int32_t))))) return rc;  // stats | bhat | total_p | nobs_p
   uint8_t* pk = (uint8_t*)ctx->pbuf[Q_PK];
   int32_t* cnt = (int32_t*)ctx->pbuf[Q_CNT];
@@ -1402,6 +1410,7 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   int32_t* nobs = (int32_t*)(vstat + (size_t)bs * 4);
   int32_t* ign = nobs + bs;
   int32_t* recheck = ign + bs;
+  int32_t* sparse = recheck + bs;
   double* stats = (double*)ctx->pbuf[Q_STAT];
   double* bhat = stats + (size_t)bs * P;
   double* total_p = bhat + (size_t)bs * P;
@@ -1467,7 +1476,11 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   fa.zeros_min = ctx->rule_zero_count ? (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * ctx->rule_thr : -1.0;
   fa.stats = stats; fa.bhat = bhat; fa.scale_fac = sf; fa.mean = mu; fa.total_p = total_p; fa.nobs = nobs; fa.ignored = ign; fa.nobs_p = nobs_p;
   fa.recheck = masked ? recheck : nullptr;
+  fa.sparse_out = sparse;
   hipLaunchKernelGGL(k_s2_packed_final, dim3((bs * P + 255) / 256), dim3(256), 0, ctx->st, fa);
+  rg_s2_ctx::LastQt lq;
+  lq.kind = 2; lq.rows = pk; lq.ld = ldp; lq.bs = bs; lq.scale = 1; lq.sf = sf; lq.mu = mu; lq.sparse = sparse;
+  ctx->last_qt = lq;
   S2_HIP(hipEventRecord(ctx->e1, ctx->st));
   S2_HIP(hipGetLastError());
   if (out->stats) S2_HIP(hipMemcpyAsync(out->stats, stats, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
@@ -1509,7 +1522,9 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
       if (out->stats) memcpy(out->stats + j * P, t_stats.data() + k * P, sizeof(double) * P);
       if (out->bhat) memcpy(out->bhat + j * P, t_bhat.data() + k * P, sizeof(double) * P);
       if (out->scale_fac) out->scale_fac[j] = t_sf[k];
+      lq.sf_fix.emplace_back((int32_t)j, t_sf[k]);      // rg_s2_qt_moments rescales by what the caller was given
     }
+    ctx->last_qt = lq;      // the block last scored is this one, not the re-examined rows
   }
   return RG_S2_OK;
 }
@@ -1542,7 +1557,7 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   if ((rc = ensure_p(ctx, Q_CNT, ((size_t)bs * 4 + 8) * sizeof(int32_t)))) return rc;
   if ((rc = ensure_p(ctx, Q_S, (size_t)ngrp * nset * nseg * n128 * 128 * sizeof(int32_t)))) return rc;
   if ((rc = ensure_p(ctx, Q_A, (size_t)bs * 2 * ctx->Cvt * sizeof(double)))) return rc;
-  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 2 * sizeof(int32_t))))) return rc;
+  if ((rc = ensure_p(ctx, Q_VAR, (size_t)bs * (6 * sizeof(double) + 3 * sizeof(int32_t))))) return rc;      // ... | nobs | ignored | sparse
   if ((rc = ensure_p(ctx, Q_STAT, (size_t)bs * P * (3 * sizeof(double) + sizeof(int32_t))))) return rc;
   if ((rc = ensure(ctx, B_PLANES, (size_t)nset * bs * Np))) return rc;
   const int64_t ld8 = (n + 7) / 8 * 8;       // staged rows start on 16-byte boundaries
@@ -1569,6 +1584,7 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   double* vstat = mu + bs;
   int32_t* nobs = (int32_t*)(vstat + (size_t)bs * 4);
   int32_t* ign = nobs + bs;
+  int32_t* sparse = ign + bs;
   double* stats = (double*)ctx->pbuf[Q_STAT];
   double* bhat = stats + (size_t)bs * P;
   double* total_p = bhat + (size_t)bs * P;
@@ -1607,7 +1623,11 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   fa.zeros_min = ctx->rule_zero_count ? (double)(ctx->rule_n > 0 ? ctx->rule_n : n) * ctx->rule_thr : -1.0;
   fa.stats = stats; fa.bhat = bhat; fa.scale_fac = sf; fa.mean = mu; fa.total_p = total_p; fa.nobs = nobs; fa.ignored = ign; fa.nobs_p = nobs_p;
   fa.recheck = nullptr;      // (mode 2 subtracts the masked samples' own residual sum)
+  fa.sparse_out = sparse;
   hipLaunchKernelGGL(k_s2_packed_final, dim3((bs * P + 255) / 256), dim3(256), 0, ctx->st, fa);
+  ctx->last_qt.sf_fix.clear();
+  ctx->last_qt.kind = 3; ctx->last_qt.rows = dG; ctx->last_qt.ld = ldg; ctx->last_qt.bs = bs; ctx->last_qt.scale = scale;
+  ctx->last_qt.sf = sf; ctx->last_qt.mu = mu; ctx->last_qt.sparse = sparse;
   S2_HIP(hipEventRecord(ctx->e1, ctx->st));
   S2_HIP(hipGetLastError());
   if (out->stats) S2_HIP(hipMemcpyAsync(out->stats, stats, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
@@ -1651,6 +1671,7 @@ int rg_s2_set_columns(rg_s2_ctx* ctx, int32_t n_col, const double* cols, int32_t
 int rg_s2_contract_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip,
                           const rg_s2_contract_out* out) {
   if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_packed: context was not created");
+  ctx->last_qt.kind = 0;      // the staging buffers of a scored block are reused below: rg_s2_qt_moments has no block any more
   if (ctx->g_ncol < 1) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_packed: rg_s2_set_columns has not been called");
   const int64_t n = ctx->n, nbytes = (n + 3) / 4;
   if (!rows || !out || bs < 1 || ld < nbytes) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_packed: bad arguments (need bs >= 1, ld >= ceil(n / 4))");
@@ -1706,6 +1727,7 @@ int rg_s2_contract_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
 
 int rg_s2_contract_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int32_t scale, const rg_s2_contract_out* out) {
   if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_int: context was not created");
+  ctx->last_qt.kind = 0;      // the staging buffers of a scored block are reused below: rg_s2_qt_moments has no block any more
   if (ctx->g_ncol < 1) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_int: rg_s2_set_columns has not been called");
   const int64_t n = ctx->n;
   if (!G || !out || bs < 1 || ld < n || scale < 1 || scale > 16384)

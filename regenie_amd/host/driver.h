@@ -120,6 +120,10 @@ struct Params {
   // covariates and leave the tested set (Regenie.cpp:217-219, :277, :516, :714-722; condition_variants in driver_inputs.cpp)
   std::string condition_list, condition_fmt, condition_file, condition_sample;
   uint32_t max_condition_vars = 10000;
+  // --step 2 --qt --mcc [--mcc-thr p] [--mcc-skew s]: the moment-matched correlation test of skewed quantitative traits (Regenie.cpp:343-345, :489,
+  // :1262-1277; compute_score_qt_mcc, Step2_Models.cpp:237-341)
+  bool mcc = false;
+  double mcc_thr = 0.01, mcc_skew = 0.0;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards
@@ -243,6 +247,9 @@ struct Run {
   // index in the main genotype file (-1: not met among the variants the chromosome / range filter leaves)
   std::map<std::string, int64_t> cond_snps;
   int n_cond = 0;                        // columns appended to the covariates (not counted in the log's n_cov, as in the reference)
+  // --mcc: params.mcc_test once the phenotypes are read (off when --mcc-skew leaves no trait), pheno_data.mcc_Y per trait (Pheno.cpp:117-131)
+  bool mcc_test = false;
+  std::vector<uint8_t> mcc_Y;
   Run() = default;
   Run(const Run&) = delete;
   ~Run() { if (pgen) rg_pgen_close(pgen); if (bgenh) rg_bgen_close(bgenh); }
@@ -324,6 +331,14 @@ double get_pvec1(double eta);
 bool solve_dense(std::vector<double> A, std::vector<double> b, int n, std::vector<double>& x);
 double norm_quantile(double p);
 double get_logp(double t);
+// --mcc: the closed-form part of the moment-matched correlation test (MCC::setup_y / precomp_sumy, MCCResults::dkat)
+struct MccTrait { double n_mask, ni, ybar, ynorm, y2, y3, y4, y6; };      // per trait and chromosome: counts, mean and norm of yres, power sums of the normalised yres
+MccTrait mcc_setup_trait(const double* yres, const uint8_t* mask, int64_t n, int n_cov);
+// sums: S_1 .. S_6 and r . yres of rg_s2_qt_moments.  -> the p-value; ok = false when the gamma fit is not defined (skewness of D <= 0) or p is 0 or 1
+double mcc_pvalue(const MccTrait& t, const double* sums, bool* ok);
+double gamma_q(double a, double x);            // regularised upper incomplete gamma Q(a, x)
+double gamma_p(double a, double x);            // ... and the lower one
+double chisq1_upper_quantile(double p);        // x with P(chi-square(1) > x) = p
 bool spd_logdet_inv(const std::vector<double>& A, int n, double& logdet, std::vector<double>* inv);
 struct LogisticState { std::vector<double> beta, pv, eta; };      // what an attempt of fit_logistic leaves for the next one (the reference's in-place arguments)
 bool fit_logistic(const double* y, const double* X, const uint8_t* mask, int64_t N, int C, const Params& prm, bool check_hs_dev, std::vector<double>& eta,

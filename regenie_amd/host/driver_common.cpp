@@ -353,6 +353,9 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--use-null-firth") p.use_null_firth = need(i);
     else if (a == "--pThresh") p.pthresh = atof(need(i).c_str());
     else if (a == "--spa") p.spa = true;
+    else if (a == "--mcc") p.mcc = true;
+    else if (a == "--mcc-thr") p.mcc_thr = atof(need(i).c_str());
+    else if (a == "--mcc-skew") p.mcc_skew = atof(need(i).c_str());
     else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
     else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
     else if (a == "--forcein-vars") p.forcein_vars = true;
@@ -448,6 +451,10 @@ Params parse_args(int argc, char** argv) {
     if (p.set_min_info && (p.min_info < 0 || p.min_info > 1)) usage_error("minimum info score must be in [0,1].");
     if (p.force_collectives) usage_error("--force-collectives applies to step 1 (step 2 has no collective: its blocks are independent).");
   }
+  if (p.mcc_skew < 0) usage_error("absolute phenotypic skewness must be positive");                            // Regenie.cpp:1262-1269
+  if (p.mcc_skew > 0 && !p.mcc) usage_error("--mcc must be on when specifying absolute phenotypic skewness");
+  // (the reference's range check of --mcc-thr, `thr > 1 && thr <= 0`, never fires: any value is taken -- at 1 or above every test is re-tested,
+  // at 0 or below none passes the threshold -- and so it is here)
   if (!p.use_null_firth.empty() && !(p.step == 2 && p.firth && p.firth_approx)) usage_error("option --use-null-firth only wors with approximate Firth test.");   // Regenie.cpp:1216-1217
   if (p.write_null_firth && ((p.step == 2 && !(p.firth && p.firth_approx)) || (p.step == 1 && !p.bt))) {   // Regenie.cpp:1218-1222
     std::cout << "WARNING: option --write-null-firth only works for BTs with approximate Firth test.\n";

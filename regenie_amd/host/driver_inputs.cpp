@@ -1030,6 +1030,25 @@ void read_pheno_cov(Run& r) {  // Pheno.cpp:50-146, :148-364, :573-808, :810-841
       }
     }
   }
+  if (p.mcc && !p.compute_corr) {      // compute_skew / skew_pheno (Pheno.cpp:117-131, :2017-2046): after RINT, before the imputation
+    sout << "   -computing phenotypic skewness: ";
+    r.mcc_test = true;
+    r.mcc_Y.assign(r.P, 1);
+    int n_use = 0;
+    for (int q = 0; q < r.P; ++q) {      // computed for every trait whatever --mcc-skew is: an all-missing trait stops the run here
+      double nv = 0.0, sum = 0.0, m2 = 0.0, m3 = 0.0;
+      for (int64_t i = 0; i < N; ++i) if (r.Y[(size_t)q * N + i] != MISSING && r.mask[(size_t)q * N + i]) { nv += 1.0; sum += r.Y[(size_t)q * N + i]; }
+      if (nv == 0.0) throw std::runtime_error("skew_pheno: all values are missing");
+      const double mean = sum / nv;
+      for (int64_t i = 0; i < N; ++i)
+        if (r.Y[(size_t)q * N + i] != MISSING && r.mask[(size_t)q * N + i]) { const double d = r.Y[(size_t)q * N + i] - mean; m2 += d * d; m3 += d * d * d; }
+      const double skew = (m3 / nv) / std::pow(m2 / nv, 1.5);
+      if (p.mcc_skew != 0.0) r.mcc_Y[q] = std::fabs(skew) > p.mcc_skew ? 1 : 0;
+      n_use += r.mcc_Y[q];
+    }
+    if (n_use == 0) r.mcc_test = false;      // --mcc-skew left no trait: the score test alone
+    sout << n_use << " phenotypes will use the MCC test\n";
+  }
   // pheno_impute_miss (QT): missing -> mean over analysed non-missing, then mask
   for (int q = 0; q < r.P && (p.bt || p.ct || p.t2e); ++q) {  // non-QT: mean over the unmasked entries (Pheno.cpp:1921-1930)
     double total = 0.0, ns = 0.0;

@@ -403,6 +403,152 @@ double get_logp(double t) {
   return -lp;
 }
 
+// ---- `--mcc`: the moment-matched correlation test of a quantitative trait (MCC.cpp) ------------------------------------------------------
+// The statistic is D = cor(x, y)^2 over the samples of the trait, x the genotype vector the score test has built, y the trait's residual.  Under
+// permutations of the samples D has moments that are polynomials in the power sums of the two NORMALISED vectors (centred, unit norm); a
+// gamma distribution with D's mean, variance and skewness gives the p-value.  Three habits of the reference are kept: every `n` of the moment
+// formulas -- the divisor of the genotype's mean included -- is Neff - K (unmasked samples minus covariates), the count of unmasked samples
+// itself enters only where a sum runs over them, and a statistic left of the fitted gamma's origin gets p = 0.99999.
+
+// log(1 + u) - u, without the cancellation at small u
+static double log1p_minus(double u) {
+  if (std::fabs(u) > 0.3) return std::log1p(u) - u;
+  double term = -u, sum = 0.0;         // -u^2/2 + u^3/3 - ...
+  for (int k = 2; k < 200; ++k) {
+    term *= -u;                        // (-1)^k u^k
+    const double add = -term / k;      // (-1)^(k+1) u^k / k
+    sum += add;
+    if (std::fabs(add) < 1e-17 * std::fabs(sum)) break;
+  }
+  return sum;
+}
+// x^a e^-x / Gamma(a + 1).  Large a: through a (log(x / a) - x / a + 1) and Stirling's series, so that nothing of size a log a is cancelled
+static double gamma_prefactor(double a, double x) {
+  if (a < 30.0) return std::exp(a * std::log(x) - x - std::lgamma(a + 1.0));
+  const double u = (x - a) / a, a2 = a * a;
+  const double stirling = 1.0 / (12.0 * a) - 1.0 / (360.0 * a * a2) + 1.0 / (1260.0 * a2 * a2 * a) - 1.0 / (1680.0 * a2 * a2 * a2 * a);
+  return std::exp(a * log1p_minus(u) - stirling) / std::sqrt(2.0 * M_PI * a);
+}
+// lower = true: P(a, x), else Q(a, x); the series below the mode, the continued fraction (modified Lentz) above it
+static double gamma_pq(double a, double x, bool lower) {
+  if (!(a > 0.0) || std::isnan(x)) return NAN;
+  if (x <= 0.0) return lower ? 0.0 : 1.0;
+  if (std::isinf(x)) return lower ? 1.0 : 0.0;
+  const double pre = gamma_prefactor(a, x);
+  const int max_it = 200 + (int)(40.0 * std::sqrt(a));
+  if (x < a + 1.0) {
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < max_it; ++k) {
+      term *= x / (a + k);
+      sum += term;
+      if (term < sum * 1e-17) break;
+    }
+    const double P = pre * sum;
+    return lower ? P : 1.0 - P;
+  }
+  const double tiny = 1e-300;
+  double b = x + 1.0 - a, c = 1.0 / tiny, d = 1.0 / b, h = d;
+  for (int k = 1; k < max_it; ++k) {
+    const double an = -(double)k * ((double)k - a);
+    b += 2.0;
+    d = an * d + b; if (std::fabs(d) < tiny) d = tiny;
+    c = b + an / c; if (std::fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (std::fabs(del - 1.0) < 1e-16) break;
+  }
+  const double Q = pre * a * h;          // e^-x x^a / Gamma(a) * the fraction
+  return lower ? 1.0 - Q : Q;
+}
+double gamma_q(double a, double x) { return gamma_pq(a, x, false); }
+double gamma_p(double a, double x) { return gamma_pq(a, x, true); }
+double chisq1_upper_quantile(double p) {
+  const double z = norm_quantile(0.5 * p);      // the lower tail keeps its digits where 1 - p / 2 would round to 1
+  return z * z;
+}
+
+MccTrait mcc_setup_trait(const double* yres, const uint8_t* mask, int64_t n, int n_cov) {
+  MccTrait t;
+  double cnt = 0.0, sum = 0.0;
+  for (int64_t i = 0; i < n; ++i) if (mask[i]) { cnt += 1.0; sum += yres[i]; }
+  t.n_mask = cnt; t.ni = cnt - (double)n_cov; t.ybar = sum / cnt;
+  double ss = 0.0;
+  for (int64_t i = 0; i < n; ++i) if (mask[i]) { const double d = yres[i] - t.ybar; ss += d * d; }
+  t.ynorm = std::sqrt(ss);
+  t.y2 = t.y3 = t.y4 = t.y6 = 0.0;
+  for (int64_t i = 0; i < n; ++i)
+    if (mask[i]) {
+      const double d = (yres[i] - t.ybar) / t.ynorm, d2 = d * d;
+      t.y2 += d2; t.y3 += d2 * d; t.y4 += d2 * d2; t.y6 += d2 * d2 * d2;
+    }
+  return t;
+}
+
+namespace {
+// the power sums of one normalised vector as the moment formulas use them: A = sum v^2, A2 = A^2, A3 = A^3, Q = sum v^4, H = sum v^6,
+// U = (sum v^3)^2, R = A Q
+struct MccSide { double A, A2, A3, Q, H, U, R; };
+MccSide mcc_side(double s2, double s3, double s4, double s6) { return {s2, s2 * s2, s2 * s2 * s2, s4, s6, s3 * s3, s2 * s4}; }
+}  // namespace
+
+double mcc_pvalue(const MccTrait& t, const double* S, bool* ok) {
+  *ok = false;
+  const double n = t.ni, n2 = n * n, n3 = n2 * n, n4 = n2 * n2;
+  // the genotype side: centred at S_1 / (Neff - K), central power sums by the binomial expansion with S_0 = the unmasked count
+  const double m = S[0] / n, S0 = t.n_mask;
+  const double m2 = m * m, m3 = m2 * m, m4 = m2 * m2, m5 = m4 * m, m6 = m3 * m3;
+  const double c2 = S[1] - 2.0 * m * S[0] + m2 * S0;
+  const double c3 = S[2] - 3.0 * m * S[1] + 3.0 * m2 * S[0] - m3 * S0;
+  const double c4 = S[3] - 4.0 * m * S[2] + 6.0 * m2 * S[1] - 4.0 * m3 * S[0] + m4 * S0;
+  const double c6 = S[5] - 6.0 * m * S[4] + 15.0 * m2 * S[3] - 20.0 * m3 * S[2] + 15.0 * m4 * S[1] - 6.0 * m5 * S[0] + m6 * S0;
+  const double xn = std::sqrt(c2), xn2 = xn * xn;
+  if (!(xn > 0.0) || !(t.ynorm > 0.0)) return NAN;
+  const MccSide x = mcc_side(c2 / xn2, c3 / (xn2 * xn), c4 / (xn2 * xn2), c6 / (xn2 * xn2 * xn2)), y = mcc_side(t.y2, t.y3, t.y4, t.y6);
+  // D: sum mask (r - m) (yres - ybar) = r . yres - ybar S_1 (the m terms cancel: sum mask (yres - ybar) = 0)
+  const double rho = (S[6] - t.ybar * S[0]) / (xn * t.ynorm), D = rho * rho;
+  // first two moments
+  const double mean = x.A * y.A / n;
+  const double va = 2.0 * ((n - 1.0) * y.A2 - y.A2) * ((n - 1.0) * x.A2 - x.A2) / ((n - 1.0) * (n - 1.0) * (n + 1.0) * (n - 2.0));
+  const double vy = n * (n + 1.0) * y.Q - (n - 1.0) * (y.A2 + 2.0 * y.A2), vx = n * (n + 1.0) * x.Q - (n - 1.0) * (x.A2 + 2.0 * x.A2);
+  const double var = va + vy * vx / ((n + 1.0) * n * (n - 1.0) * (n - 2.0) * (n - 3.0));
+  // third raw moment: every term is symmetric in the two sides; sym(f, g) = f(x) g(y) + f(y) g(x)
+  auto sym = [](double fx, double gy, double fy, double gx) { return fx * gy + fy * gx; };
+  const double AQx = x.A * x.Q, AQy = y.A * y.Q;            // (= R; named for the terms where the reference writes T S2)
+  const double AA2x = x.A * x.A2, AA2y = y.A * y.A2;        // T T2
+  double e3 = 0.0;
+  e3 += n2 * (n + 1.0) * (n2 + 15.0 * n - 4.0) * y.H * x.H;
+  e3 += 4.0 * (n4 - 8.0 * n3 + 19.0 * n2 - 4.0 * n - 16.0) * y.U * x.U;
+  e3 += 24.0 * (n2 - n - 4.0) * 2.0 * y.U * x.U;
+  e3 += 6.0 * (n4 - 8.0 * n3 + 21.0 * n2 - 6.0 * n - 24.0) * y.U * x.U;
+  e3 += 12.0 * (n4 - n3 - 8.0 * n2 + 36.0 * n - 48.0) * y.R * x.R;
+  e3 += 12.0 * (n3 - 2.0 * n2 + 9.0 * n - 12.0) * sym(x.R, AQy, y.R, AQx);
+  e3 += 3.0 * (n4 - 4.0 * n3 - 2.0 * n2 + 9.0 * n - 12.0) * AQy * AQx;
+  e3 += 24.0 * ((n3 - 3.0 * n2 - 2.0 * n + 8.0) + (n3 - 2.0 * n2 - 3.0 * n + 12.0)) * sym(x.U, y.R, y.U, x.R);
+  e3 += 12.0 * (n2 - n + 4.0) * sym(x.U, AQy, y.U, AQx);
+  e3 += 6.0 * (2.0 * n3 - 7.0 * n2 - 3.0 * n + 12.0) * sym(x.U, AQy, y.U, AQx);
+  e3 += -2.0 * n * (n - 1.0) * (n2 - n + 4.0) * 5.0 * sym(x.H, y.U, y.H, x.U);
+  e3 += -3.0 * n * (n - 1.0) * (n - 1.0) * (n + 4.0) * sym(x.H, AQy + 4.0 * y.R, y.H, AQx + 4.0 * x.R);
+  e3 += 2.0 * n * (n - 1.0) * (n - 2.0) * sym(x.H, y.A3 + 6.0 * AA2y + 8.0 * y.A3, y.H, x.A3 + 6.0 * AA2x + 8.0 * x.A3);
+  e3 += y.A3 * ((n3 - 9.0 * n2 + 23.0 * n - 14.0) * x.A3 + 6.0 * (n - 4.0) * AA2x + 8.0 * x.A3);
+  e3 += 6.0 * AA2y * ((n - 4.0) * x.A3 + (n3 - 9.0 * n2 + 24.0 * n - 14.0) * AA2x + 4.0 * (n - 3.0) * x.A3);
+  e3 += 8.0 * y.A3 * (x.A3 + 3.0 * (n - 3.0) * AA2x + (n3 - 9.0 * n2 + 26.0 * n - 22.0) * x.A3);
+  e3 += -16.0 * sym(x.U, y.A3, y.U, x.A3) - 6.0 * (2.0 * n2 - 10.0 * n + 16.0) * sym(x.U, AA2y, y.U, AA2x);
+  e3 += -8.0 * (3.0 * n2 - 15.0 * n + 16.0) * sym(x.U, y.A3, y.U, x.A3) - (6.0 * n2 - 30.0 * n + 24.0) * sym(x.U, y.A3, y.U, x.A3);
+  e3 += -6.0 * (4.0 * n2 - 20.0 * n + 24.0) * sym(x.U, AA2y, y.U, AA2x) - 8.0 * (3.0 * n2 - 15.0 * n + 24.0) * sym(x.U, y.A3, y.U, x.A3);
+  double tail = 24.0 * sym(x.R, y.A3, y.R, x.A3) + 6.0 * (2.0 * n2 - 10.0 * n + 24.0) * sym(x.R, AA2y, y.R, AA2x);
+  tail += 8.0 * (3.0 * n2 - 15.0 * n + 24.0) * sym(x.R, y.A3, y.R, x.A3) + (3.0 * n2 - 15.0 * n + 6.0) * sym(AQx, y.A3, AQy, x.A3);
+  tail += 6.0 * (n2 - 5.0 * n + 6.0) * sym(AQx, AA2y, AQy, AA2x) + 48.0 * sym(AQx, y.A3, AQy, x.A3);
+  e3 += -(n - 2.0) * tail;
+  e3 /= n * (n - 1.0) * (n - 2.0) * (n - 3.0) * (n - 4.0) * (n - 5.0);
+  const double skew = (e3 - 3.0 * mean * var - mean * mean * mean) / std::pow(var, 1.5);
+  if (!(skew > 0.0) || !(var > 0.0)) return NAN;
+  const double shape = 4.0 / (skew * skew), scale = std::sqrt(var) * skew / 2.0, origin = mean - 2.0 * std::sqrt(var) / skew;
+  const double pv = D - origin < 0.0 ? 0.99999 : gamma_q(shape, (D - origin) / scale);
+  *ok = pv > 0.0 && pv < 1.0;
+  return pv;
+}
+
 // ---- `--step 2`: single-variant additive tests (Data::test_snps_fast, Data.cpp:2230-2360) --------------------------------------------
 // Host side: the LOCO reader (blup_read / blup_read_chr, Pheno.cpp:1241-1391, Step2_Models.cpp:51-140), per chromosome compute_res
 // (Data.cpp:2386-2400) or the null logistic / Poisson (/ Firth) model of compute_res_bin / compute_res_count, the per-variant bookkeeping

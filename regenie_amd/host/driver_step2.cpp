@@ -15,6 +15,7 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p)
     for (int q = 0; q < P; ++q)
       if (!r.mask[(size_t)q * N + an[k]]) { has_missing[k] = 1; any_missing = true; }
   glm = p.bt || p.ct;                                 // binary / count traits: the score test of a generalised linear null model
+  mcc = r.mcc_test && !glm;                           // --mcc: quantitative traits only (the reference ignores it elsewhere, apart from the log line)
   Xc.resize((size_t)C * n); Yc.resize((size_t)P * n); Mc.resize((size_t)P * n);
   for (int c = 0; c < C; ++c) for (int64_t k = 0; k < n; ++k) Xc[(size_t)c * n + k] = r.X[(size_t)c * N + an[k]];
   for (int q = 0; q < P; ++q)
@@ -91,6 +92,7 @@ struct ChromNull {
   std::vector<uint8_t> bt_pass;
   std::vector<double> firth_off;                      // [P][n] cov_blup_offset: X beta_nullFirth + LOCO prediction (fit_null_firth, Step2_Models.cpp:1011-1013)
   std::vector<double> firth_bnull, blup_off;          // exact Firth: the covariate-only estimates (start values), the LOCO offsets
+  std::vector<MccTrait> mcc_traits;                   // --mcc: setup_y's per-trait sums of the chromosome's residuals
   std::vector<std::string> null_firth_files, firth_file_body;       // --use-null-firth: per-trait files of the list; --write-null-firth: what goes out
   double ms_chr = 0;
 
@@ -248,7 +250,13 @@ struct ChromNull {
       nm.family = p.ct ? 1 : 0; nm.niter_max = p.niter_max; nm.X = cm.Xc.data(); nm.y = cm.Yc.data(); nm.mask = cm.Mc.data(); nm.fitted = bt_fit.data();
       nm.firth_offset = (cm.firth && p.firth_approx) ? firth_off.data() : nullptr; nm.pass = bt_pass.data();
       rc = rg_s2_bt_set_null(s2, &nm);
-    } else rc = rg_s2_set_null(s2, cm.Xc.data(), resc.data(), cm.Mc.data(), scf.data());
+    } else {
+      rc = rg_s2_set_null(s2, cm.Xc.data(), resc.data(), cm.Mc.data(), scf.data());
+      if (cm.mcc) {
+        mcc_traits.resize(cm.P);
+        for (int q = 0; q < cm.P; ++q) mcc_traits[q] = mcc_setup_trait(resc.data() + (size_t)q * n, cm.Mc.data() + (size_t)q * n, n, cm.C);
+      }
+    }
     if (rc != RG_S2_OK) throw std::runtime_error(rg_s2_last_error(s2));
     sout << "done (" << std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - tb).count() << "ms) \n";
     ms_chr += ms_since(tb);
@@ -289,6 +297,8 @@ struct S2Block {
   std::vector<double> stats, bhat, sfac, denum_v, mu_v, corr_beta, corr_se, corr_chisq, corr_logp;
   std::vector<int32_t> ign;
   std::vector<uint8_t> test_ignored, sparse_v, corrected, corr_fail;
+  std::vector<double> mcc_logp, mcc_se_mult;        // --mcc, per (variant, trait): -log10 p of the test (NaN: the score test stands), factor on SE
+  std::vector<uint8_t> mcc_fail;
 
   void begin(int bs_) {
     bs = bs_;
@@ -438,6 +448,52 @@ struct S2Block {
     }
   }
 
+  // --mcc (compute_score_qt_mcc, Step2_Models.cpp:237-341): the rows that need the test -- with --mcc-thr 1 every kept row, else the rows with a
+  // qualifying trait whose score test passes the threshold, and every kept SPARSE row: the reference forms the statistic of this mode from the
+  // vector the MCC sees, which for a sparse variant is the raw genotype (sum mask g^2 as denominator, not the residualised one of the plain
+  // score test), so its BETA / SE / CHISQ come from the same sums -- one rg_s2_qt_moments call, then the closed form per (row, trait)
+  void mcc(const BlockCounts& bc) {
+    const Params& p = cm.p;
+    const int P = cm.P;
+    const bool every = !(p.mcc_thr < 1.0);
+    const double thr_nlog10 = -std::log10(p.mcc_thr);
+    mcc_logp.assign((size_t)bs * P, NAN); mcc_se_mult.assign((size_t)bs * P, 1.0); mcc_fail.assign((size_t)bs * P, 0);
+    std::vector<int32_t> todo;
+    for (int j = 0; j < bs; ++j) {
+      if (bc.variant_ignored[j] || ign[j]) continue;
+      bool need = every || sfac[j] == 1.0;       // scale_fac = 1: check_sparse_G's verdict as the score entries return it
+      for (int q = 0; q < P && !need; ++q) {
+        const double st = stats[(size_t)j * P + q];
+        need = cm.r.mcc_Y[q] && get_logp(st * st) > thr_nlog10;
+      }
+      if (need) todo.push_back(j);
+    }
+    if (todo.empty()) return;
+    std::vector<double> sums(todo.size() * (size_t)P * 7);
+    rg_s2_mcc_out mo;
+    mo.sums = sums.data();
+    check(rg_s2_qt_moments(s2, (int32_t)todo.size(), todo.data(), &mo));
+    parallel_for((int)todo.size(), cm.nthreads, [&](int t) {
+      const int j = todo[t];
+      for (int q = 0; q < P; ++q) {
+        const size_t e = (size_t)j * P + q;
+        const double* S = sums.data() + ((size_t)t * P + q) * 7;
+        if (sfac[j] == 1.0) {      // the non-strict statistic on the vector as it is (gsc = 1)
+          const double sd = std::sqrt(S[1]);
+          stats[e] = S[6] / sd;
+          bhat[e] = stats[e] * null.scf[q] / sd;
+        }
+        const double chisq = stats[e] * stats[e];
+        if (!every && !(cm.r.mcc_Y[q] && get_logp(chisq) > thr_nlog10)) continue;
+        bool ok = false;
+        const double pv = mcc_pvalue(null.mcc_traits[q], S, &ok);
+        if (!ok) { mcc_fail[e] = 1; mcc_logp[e] = -1.0; continue; }
+        mcc_logp[e] = -std::log10(pv);
+        mcc_se_mult[e] = std::sqrt(chisq / chisq1_upper_quantile(pv));
+      }
+    });
+  }
+
   // binary / count traits: the score test of the block through the C ABI (rg_s2_bt_score_*: contractions on the i8 matrix cores, C x C
   // algebra in the library): hard calls as packed rows, dosages as integer rows
   void score_glm(BlockCounts& bc) {
@@ -583,7 +639,12 @@ struct S2Block {
             if (corr_fail[e]) test_fail = true;                    // get_sumstats(true, ...): the score test's BETA / SE, no p-value
             else { bh = corr_beta[e]; se = corr_se[e]; chisq = corr_chisq[e]; logp_spa = corr_logp[e]; }
           }
-          const double logp = logp_spa >= 0 ? logp_spa : get_logp(chisq);       // --spa prints the p-value it computed, the chi-square is derived from it
+          double logp_mcc = NAN;
+          if (cm.mcc && !std::isnan(mcc_logp[e])) {      // LOG10P of the moment-matched test, SE scaled to it; BETA and CHISQ stay
+            if (mcc_fail[e]) test_fail = true;
+            else { logp_mcc = mcc_logp[e]; se *= mcc_se_mult[e]; }
+          }
+          const double logp = !std::isnan(logp_mcc) ? logp_mcc : logp_spa >= 0 ? logp_spa : get_logp(chisq);       // --spa prints the p-value it computed, the chi-square is derived from it
           std::ostringstream ln;
           if (af >= 0) ln << head.str() << af << " ";            // print_sum_stats_single (Step2_Models.cpp:2505-2518): a negative value is "NA"
           else ln << head.str() << "NA ";
@@ -678,6 +739,7 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
       // score, correct, format
       if (cm.glm) blk.score_glm(bc); else blk.score_qt(bc);
       if (cm.glm && cm.correct) blk.correct(bc);
+      if (cm.mcc) blk.mcc(bc);
       auto t_fmt = std::chrono::steady_clock::now();
       ms_device += std::chrono::duration<double, std::milli>(t_fmt - t_dev).count();
       blk.format(bc, snps, j0, ofs, n_ign);

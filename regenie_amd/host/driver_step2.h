@@ -79,7 +79,7 @@ struct S2Common : SampleMap {
   std::vector<uint8_t> Mc;
   std::map<int, std::vector<int64_t>> chr_snps; // blocks per chromosome (set_blocks_for_testing: ceil(n_chr / bsize))
   int total_blocks = 0;
-  bool glm, firth, spa, correct, per_trait, show_info, multi, fast_bgen;
+  bool glm, mcc, firth, spa, correct, per_trait, show_info, multi, fast_bgen;
   double z_thr;
   In in;
   int flip, dscale, nthreads, nt_prep;

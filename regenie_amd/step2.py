@@ -36,6 +36,10 @@ class _BtCorr(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class _MccOut(C.Structure):
+    _fields_ = [("sums", C.c_void_p)]
+
+
 BT_FIRTH_APPROX, BT_SPA = 1, 2
 
 
@@ -160,6 +164,17 @@ class Step2QT:
         out = _QtOut(*[res[k].ctypes.data for k in ("stats", "bhat", "scale_fac", "mean", "n_obs", "ignored")])
         self._check(self.lib.rg_s2_qt_block_int(self.h, ptr, ld, bs, on_device, int(scale), float(numtol), C.byref(out)))
         return self._finish(res)
+
+    def qt_moments(self, variant) -> dict:
+        """The sums of the moment-matched test (`--mcc`) for the listed rows of the block LAST scored by score_block / score_block_packed /
+        score_block_int: sums [nv][P][7] = S_1 .. S_6 (sum_i mask_t r^k) and r . yres_t, r = the vector the reference's MCC sees (raw mean-imputed
+        genotype of a sparse variant, the residualised and rescaled one otherwise).  A device tensor handed to the score call must still be alive."""
+        variant = np.ascontiguousarray(variant, dtype=np.int32).ravel()
+        res = {"sums": np.zeros((variant.size, self.P, 7))}
+        out = _MccOut(res["sums"].ctypes.data)
+        self._check(self.lib.rg_s2_qt_moments(self.h, variant.size, variant.ctypes.data, C.byref(out)))
+        res["kernel_ms"] = self.lib.rg_s2_last_kernel_ms(self.h)
+        return res
 
     # ---- the contraction primitive (rg_s2_set_columns / rg_s2_contract_packed) ------------------------------------------------
     def set_columns(self, cols: np.ndarray, n_sq: int = 0) -> None:

@@ -51,6 +51,11 @@ int rg_bgen_read_dosages(rg_bgen* h, int64_t n, const int64_t* variant_idx, int3
  * 4 prob0 + prob1 - G^2, or with ref_first 4 prob2 + prob1 - G^2; 0 for a missing sample): info_rows has the layout of rows. */
 int rg_bgen_read_dosages_info(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows,
                               int64_t row_stride);
+/* The same, plus the value the dominant (coding 1) / recessive (coding 2) test of Step 2 takes in the dosage's place (`--test`, parseSnpfromBGEN,
+ * Geno.cpp:2362-2392): coded_rows = prob0 + prob1 / prob0, with ref_first prob1 + prob2 / prob2 (prob2 = max(1 - prob0 - prob1, 0)); -3 = missing;
+ * coding 0: the dosage again.  rows keep the ADDITIVE dosage (the allele frequency, MAC and INFO of a recoded test are additive); info_rows may be NULL. */
+int rg_bgen_read_dosages_coded(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, int32_t coding, double* rows, double* info_rows,
+                               double* coded_rows, int64_t row_stride);
 /* The inflated, checked probability blocks of n variants, for a caller that walks the bytes itself (the Step-2 driver turns them into
  * 2-byte integer dosages and the allele / info sums in ONE pass instead of three double rows per variant): block k starts at
  * blocks + k * block_stride (block_stride >= rg_bgen_block_bytes = 10 + 3 N) and holds, as the file does,
@@ -84,6 +89,11 @@ const char* rg_bgen_dev_last_error(const rg_bgen_dev* d);
  * mask: [P][n] bytes, 1 = trait p is observed for sample k (NULL or P = 0: no per-trait sums; at most 2,048 traits with masks, RG_BGEN_ERR_ARG beyond:
  * the caller then keeps the host route). */
 int rg_bgen_dev_set_samples(rg_bgen_dev* d, int64_t n_file, int64_t n, const int64_t* file_idx, int32_t P, const uint8_t* mask);
+/* The decode mode of `--test dominant | recessive` (coding 1 | 2; 0, the default: the dosage): the g16 rows of the batches decoded afterwards hold
+ * P(het) + P(hom) or P(hom) of the counted allele in units of 1 / 255 (b0 + b1 | b0, with ref_first b1 + b2 | b2, b2 = max(255 - b0 - b1, 0); at most
+ * 255 in a file whose probabilities sum to at most 1), as rg_bgen_read_dosages_coded's coded rows do.  Every sum of rg_bgen_dev_out -- sum_q, sum_info,
+ * max_q, the per-trait ones -- stays that of the additive dosage: one walk emits both. */
+int rg_bgen_dev_set_coding(rg_bgen_dev* d, int32_t coding);
 /* What a batch leaves behind.  The host arrays may be NULL (not wanted); g16 / raw are DEVICE pointers owned by the decoder, valid until the
  * next call on the same slot.  Sums run over the analysed samples whose genotype is not missing:
  *   sum_q = sum q_i (q = b1 + 2 b0, or b1 + 2 max(255 - b0 - b1, 0) with ref_first: the dosage x 255);

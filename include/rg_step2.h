@@ -113,6 +113,27 @@ int rg_s2_contract_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
  * entries number >= n_samples * prop_zero_thr (.pgen input, which counts n_zero while reading, Geno.cpp:2582-2594). */
 int rg_s2_set_sparse_rule(rg_s2_ctx* ctx, int64_t n_samples, double prop_zero_thr, int32_t zero_count_rule);
 
+/* ---- `--test dominant | recessive`: the genotype coding of the tests ------------------------------------------------------------------------
+ * The reference recodes the genotype vector AFTER its additive statistics (allele count, MAC filter, INFO, per-trait counts: parseSnpfromBed,
+ * Geno.cpp:2445-2507) and BEFORE mean imputation (:2509-2532): dominant 2 -> 1, recessive 1 -> 0 and 2 -> 1; the mean that replaces a missing
+ * call is the recoded vector's; flip_geno is off (Data.cpp:2108).  rg_s2_set_coding makes the hard-call entries do the same: a kernel of its own
+ * relabels the 2-bit codes of the STAGED rows after they have been counted (dominant 00 -> 10; recessive 10 -> 11, 00 -> 10), and everything after
+ * it -- contractions, projection, check_sparse_G's verdict on the vector as tested, the corrections of rg_s2_bt_correct, rg_s2_qt_moments -- sees
+ * a hard-call row whose calls are 0 / 1 / missing.  A context whose coding is RG_S2_ADDITIVE (the default) launches nothing new.
+ *   rg_s2_qt_block_packed     stats / bhat / scale_fac / ignored / mean: of the recoded vector; n_obs: unchanged by the coding;
+ *                             total_p / n_obs_p: ADDITIVE (what update_trait_counts accumulated before the recoding)
+ *   rg_s2_contract_packed     sums / sq: of the recoded vector; counts: ADDITIVE (calls equal to 1, equal to 2 -- the count `--minHOMs` compares --, missing)
+ *   rg_s2_bt_score_packed     statistics, mean, sparse: recoded (no flip_geno); counts, total_p, n_obs_p: ADDITIVE
+ *   rg_s2_packed_counts       the additive counts [bs][4] of the block last staged by any of the three (host pointer)
+ * The .pgen form of check_sparse_G's rule keeps counting the ADDITIVE zeros (prep_snp_stats counts them while reading, Geno.cpp:2582-2594).
+ * Integer dosages (rg_s2_qt_block_int / rg_s2_bt_score_int / rg_s2_contract_int) are taken as they come: the decoder writes the coded value
+ * (include/rg_bgen.h: P(het) + P(hom) or P(hom), at most `scale`), the entries do not look at the coding. */
+#define RG_S2_ADDITIVE 0
+#define RG_S2_DOMINANT 1
+#define RG_S2_RECESSIVE 2
+int rg_s2_set_coding(rg_s2_ctx* ctx, int32_t coding);
+int rg_s2_packed_counts(rg_s2_ctx* ctx, int32_t* counts);
+
 /* ---- binary and count traits: the score test and its corrections ---------------------------------------------------
  * What it replaces in the reference (`regenie --step 2 --bt [--firth --approx | --spa]`, `--ct`):
  *   rg_s2_bt_set_null     what compute_res_bin / compute_res_count leave per chromosome (Data.cpp:2439-2455): the fitted mean of the null

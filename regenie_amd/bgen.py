@@ -63,6 +63,16 @@ class BgenFile:
         self._check(self.lib.rg_bgen_read_dosages(self.h, idx.size, idx.ctypes.data, 1 if ref_first else 0, rows.ctypes.data, self.n_samples))
         return rows
 
+    def read_dosages_coded(self, variant_idx, coding: int, ref_first: bool = False):
+        """The decode mode of `--test dominant | recessive` (coding 1 | 2; 0: the dosage): -> (dosage rows as read_dosages, coded rows), both float64
+        [len(idx), n_samples], -3 = missing.  coded = prob0 + prob1 (dominant) or prob0 (recessive); with ref_first prob1 + prob2 / prob2."""
+        idx = np.ascontiguousarray(variant_idx, dtype=np.int64)
+        rows = np.empty((idx.size, self.n_samples), dtype=np.float64)
+        coded = np.empty((idx.size, self.n_samples), dtype=np.float64)
+        self._check(self.lib.rg_bgen_read_dosages_coded(self.h, idx.size, idx.ctypes.data, 1 if ref_first else 0, int(coding), rows.ctypes.data, None,
+                                                        coded.ctypes.data, self.n_samples))
+        return rows, coded
+
     def read_blocks(self, variant_idx) -> np.ndarray:
         """uint8 [len(idx), 10 + 3 n_samples]: the inflated, checked probability blocks (rg_bgen_read_blocks) -- ploidy / missingness bytes
         at [8, 8 + N), the (prob0, prob1) byte pairs at [10 + N, 10 + 3 N)."""
@@ -129,6 +139,10 @@ class BgenDevice:
         assert mk is None or mk.shape == (P, n)
         self._check(self.lib.rg_bgen_dev_set_samples(self.h, int(n_file), n, None if fi is None else fi.ctypes.data, P, None if mk is None else mk.ctypes.data))
         self.n, self.n_file, self.P = n, int(n_file), P
+
+    def set_coding(self, coding: int) -> None:
+        """`--test`: 0 the g16 rows hold the dosage (default), 1 / 2 the dominant / recessive coded probability in 1 / 255; the sums stay additive."""
+        self._check(self.lib.rg_bgen_dev_set_coding(self.h, int(coding)))
 
     def decode(self, comp, off, clen, ulen, ref_first: bool = False, slot: int = 0, fetch_raw: bool = False):
         """Returns a dict: g16 [nvar, n] uint16 (fetched to the host), the sums, status, and with fetch_raw the inflated blocks."""

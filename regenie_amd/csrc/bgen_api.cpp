@@ -110,16 +110,22 @@ int rg_bgen_set_threads(rg_bgen* h, int32_t n_threads) {
   return RG_BGEN_OK;
 }
 
-static int read_rows(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows, int64_t row_stride);
+static int read_rows(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows, int64_t row_stride, int coding, double* coded_rows);
 
 int rg_bgen_read_dosages(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, int64_t row_stride) {
-  return read_rows(h, n, variant_idx, ref_first, rows, nullptr, row_stride);
+  return read_rows(h, n, variant_idx, ref_first, rows, nullptr, row_stride, 0, nullptr);
 }
 
 int rg_bgen_read_dosages_info(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows,
                               int64_t row_stride) {
   if (h && !info_rows) return fail(h, RG_BGEN_ERR_ARG, "rg_bgen_read_dosages_info: bad argument");
-  return read_rows(h, n, variant_idx, ref_first, rows, info_rows, row_stride);
+  return read_rows(h, n, variant_idx, ref_first, rows, info_rows, row_stride, 0, nullptr);
+}
+
+int rg_bgen_read_dosages_coded(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, int32_t coding, double* rows, double* info_rows,
+                               double* coded_rows, int64_t row_stride) {
+  if (h && (!coded_rows || coding < 0 || coding > 2)) return fail(h, RG_BGEN_ERR_ARG, "rg_bgen_read_dosages_coded: bad argument (coding 0 additive, 1 dominant, 2 recessive)");
+  return read_rows(h, n, variant_idx, ref_first, rows, info_rows, row_stride, coding, coded_rows);
 }
 int rg_bgen_block_bytes(const rg_bgen* h, int64_t* bytes) {
   if (!h || !h->ok || !bytes) return RG_BGEN_ERR_ARG;
@@ -221,7 +227,7 @@ int rg_bgen_read_compressed(rg_bgen* h, int64_t n, const int64_t* variant_idx, u
 }
 }  // extern "C"
 
-static int read_rows(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows, int64_t row_stride) {
+static int read_rows(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t ref_first, double* rows, double* info_rows, int64_t row_stride, int coding, double* coded_rows) {
   if (!h) return RG_BGEN_ERR_ARG;
   if (!h->ok) return fail(h, RG_BGEN_ERR_ARG, "bgen file is not open");
   if (n < 0 || (n > 0 && (!variant_idx || !rows)) || row_stride < (int64_t)h->rd.n_samples())
@@ -236,7 +242,8 @@ static int read_rows(rg_bgen* h, int64_t n, const int64_t* variant_idx, int32_t 
     const int64_t k0 = n * t / nt, k1 = n * (t + 1) / nt;
     try {
       for (int64_t k = k0; k < k1; ++k)
-        h->rd.read_dosages((uint32_t)variant_idx[k], ref_first != 0, rows + k * row_stride, cbuf, ubuf, info_rows ? info_rows + k * row_stride : nullptr);
+        h->rd.read_dosages((uint32_t)variant_idx[k], ref_first != 0, rows + k * row_stride, cbuf, ubuf, info_rows ? info_rows + k * row_stride : nullptr, coding,
+                            coded_rows ? coded_rows + k * row_stride : nullptr);
     } catch (const std::exception& e) {
       errs[(size_t)t] = e.what();
       if (errs[(size_t)t].empty()) errs[(size_t)t] = "bgen read failed";

@@ -629,6 +629,7 @@ struct WalkArgs {
   int W;                                          // words per sample = ceil(P / 64)
   long long* sum_q; long long* sum_info; long long* n_obs; int* max_q;      // [nvar]
   long long* sum_q_t; long long* sum_info_t; long long* n_obs_t;            // [nvar][P]: what the samples missing for trait p contribute
+  int coding;      // rg_bgen_dev_set_coding: 0 the row holds the dosage q; 1 / 2 the coded probability (the sums stay those of q)
 };
 __device__ __forceinline__ long long wave_sum_ll(long long x) {
   for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
@@ -660,7 +661,9 @@ __global__ __launch_bounds__(256) void k_bgen_walk(WalkArgs a) {
     // the sample's term of the IMPUTE-info numerator is (4 probX + prob1) - G^2: 255 (4 bX + b1) - q^2 in units of 1 / 65025
     const unsigned bx = a.ref_first ? (b0 + b1 < 255u ? 255u - b0 - b1 : 0u) : b0;
     const unsigned q = b1 + 2u * bx;
-    row[k] = (uint16_t)q;
+    // `--test dominant | recessive` (parseSnpfromBGEN's second pass, Geno.cpp:2384-2389): the row takes P(het) + P(hom) or P(hom) of the counted
+    // allele, bx being its homozygote's byte; every sum below stays additive, as the reference's A1FREQ / MAC / INFO do
+    row[k] = (uint16_t)(a.coding == 0 ? q : (a.coding == 1 ? b1 + bx : bx));
     const long long inf = 255ll * (long long)(4u * bx + b1) - (long long)q * (long long)q;
     sq += q; si += inf; no += 1;
     mq = max(mq, (int)q);
@@ -707,6 +710,7 @@ struct rg_bgen_dev {
   std::string err;
   int64_t n_file = 0, n = 0;
   int P = 0;
+  int coding = 0;
   bool identity = true;
   int64_t* d_file_idx = nullptr;
   unsigned long long* d_missbits = nullptr;      // [n][ceil(P / 64)]: the traits missing per sample
@@ -748,6 +752,13 @@ int rg_bgen_dev_create(rg_bgen_dev** out, int32_t device) {
   h->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) { delete h; return RG_BGEN_ERR_DEVICE; }
   *out = h;
+  return RG_BGEN_OK;
+}
+
+int rg_bgen_dev_set_coding(rg_bgen_dev* h, int32_t coding) {
+  if (!h) return RG_BGEN_ERR_ARG;
+  if (coding < 0 || coding > 2) { h->err = "rg_bgen_dev_set_coding: coding must be 0 (additive), 1 (dominant) or 2 (recessive)"; return RG_BGEN_ERR_ARG; }
+  h->coding = coding;
   return RG_BGEN_OK;
 }
 
@@ -843,7 +854,7 @@ int rg_bgen_dev_decode(rg_bgen_dev* h, int32_t slot, int32_t nvar, const uint8_t
   long long* d_not = d_sit + (size_t)nvar * P;
   int* d_mq = (int*)(d_not + (size_t)nvar * P);
   WalkArgs wa{s.d_raw, stride, h->n_file, h->n, h->d_file_idx, d_status, ref_first ? 1 : 0, s.d_g16, ld16, P, h->d_missbits, (P + 63) / 64,
-              d_sq, d_si, d_no, d_mq, d_sqt, d_sit, d_not};
+              d_sq, d_si, d_no, d_mq, d_sqt, d_sit, d_not, h->coding};
   hipLaunchKernelGGL(k_bgen_walk, dim3((unsigned)((ld16 + 1023) / 1024), (unsigned)nvar), dim3(256), wa.missbits ? (size_t)(3 * wa.P) * sizeof(unsigned long long) : 0, st, wa);
   BD_HIP(hipGetLastError());
   BD_HIP(hipMemcpyAsync(s.h_sums, s.d_sums, sums_bytes, hipMemcpyDeviceToHost, st));

@@ -230,16 +230,20 @@ class Reader {
   }
 
   // Dosage row of variant j: n_samples doubles, -3 = missing.
-  void read_dosages(uint32_t j, bool ref_first, double* out, std::vector<uint8_t>& cbuf, std::vector<uint8_t>& ubuf, double* info = nullptr) const {
+  // coding 1 / 2 with `coded`: the value the dominant / recessive test takes instead of the dosage (parseSnpfromBGEN, Geno.cpp:2384-2389):
+  // P(het) + P(hom) or P(hom) of the counted allele -- prob0 + prob1 / prob0, with ref_first prob1 + prob2 / prob2 -- -3 = missing.
+  void read_dosages(uint32_t j, bool ref_first, double* out, std::vector<uint8_t>& cbuf, std::vector<uint8_t>& ubuf, double* info = nullptr, int coding = 0,
+                    double* coded = nullptr) const {
     const uint8_t* blk = read_block(j, cbuf, ubuf);
     const uint8_t* ploidy = blk + 8;
     const uint8_t* pr = blk + 10 + n_;
     for (uint32_t i = 0; i < n_; ++i) {
-      if (ploidy[i] & 0x80) { out[i] = -3.0; if (info) info[i] = 0.0; continue; }
+      if (ploidy[i] & 0x80) { out[i] = -3.0; if (info) info[i] = 0.0; if (coded) coded[i] = -3.0; continue; }
       const double p0 = pr[2 * i] / 255.0, p1 = pr[2 * i + 1] / 255.0;
       const double p2 = std::max(1.0 - p0 - p1, 0.0);
       out[i] = ref_first ? p1 + 2.0 * p2 : p1 + 2.0 * p0;   // Geno.cpp:1672-1679
       if (info) info[i] = (ref_first ? 4.0 * p2 + p1 : 4.0 * p0 + p1) - out[i] * out[i];   // the sample's term of the IMPUTE info score (parseSnpfromBGEN, Geno.cpp:2292-2295)
+      if (coded) coded[i] = coding == 1 ? (ref_first ? p1 + p2 : p0 + p1) : coding == 2 ? (ref_first ? p2 : p0) : out[i];
     }
   }
 

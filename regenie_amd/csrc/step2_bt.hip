@@ -423,7 +423,10 @@ int grow(rg_s2_ctx* ctx, void** p, size_t* cap, size_t bytes) {
 
 // the score test of every (variant, trait) of the block from the contraction sums (compute_score_bt / compute_score_ct with get_sumstats)
 // n_two [bs]: observed entries equal to 2 (integer dosages; hard calls have it in counts)
-int score_from_sums(rg_s2_ctx* ctx, int bs, double numtol, const int32_t* counts, const double* vstat, const int32_t* n_two, int scale, const rg_s2_bt_out* out) {
+// add_counts (non-additive codings of hard calls: `counts` are then those of the RELABELLED row): the additive counts, whose zeros the .pgen form of
+// check_sparse_G's rule keeps counting (Geno.cpp:2582-2594)
+int score_from_sums(rg_s2_ctx* ctx, int bs, double numtol, const int32_t* counts, const double* vstat, const int32_t* n_two, int scale, const rg_s2_bt_out* out,
+                    const int32_t* add_counts = nullptr) {
   BtState& bt = *ctx->bt;
   const int P = ctx->P, C = ctx->C, ncol = bt.ncol;
   const int64_t n = ctx->n;
@@ -448,7 +451,8 @@ int score_from_sums(rg_s2_ctx* ctx, int bs, double numtol, const int32_t* counts
     bt.flip[j] = flipped ? 1 : 0;
     const double nnz_t = flipped ? nobs - ntwo : nnz, mu_t = flipped ? 2.0 - mu : mu;
     // check_sparse_G (Geno.cpp:3165-3177)
-    const bool sparse_j = ctx->rule_zero_count ? (nobs - nnz) >= Nrule * ctx->rule_thr : (nnz_t + (mu_t != 0.0 ? (double)n - nobs : 0.0)) <= Nrule * (1.0 - ctx->rule_thr);
+    const double nnz_read = add_counts ? (double)add_counts[(size_t)j * 4] + (double)add_counts[(size_t)j * 4 + 1] : nnz;
+    const bool sparse_j = ctx->rule_zero_count ? (nobs - nnz_read) >= Nrule * ctx->rule_thr : (nnz_t + (mu_t != 0.0 ? (double)n - nobs : 0.0)) <= Nrule * (1.0 - ctx->rule_thr);
     if (out->sparse) out->sparse[j] = sparse_j ? 1 : 0;
     const double* s0 = bt.sums.data() + (size_t)j * 2 * ncol;
     const double* s1 = s0 + ncol;
@@ -598,14 +602,44 @@ int rg_s2_bt_score_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   rg_s2_contract_out co;
   memset(&co, 0, sizeof(co));
   co.sums = bt.sums.data(); co.sq = bt.sq.data(); co.counts = counts.data();
+  bool all_observed = true;        // every trait observed for every sample: the per-trait counts are the variant's
+  for (int q = 0; q < P; ++q) all_observed = all_observed && bt.msum[q] == (double)ctx->n;
+  ctx->contract_mask = all_observed ? nullptr : bt.dM;      // (read under a non-additive coding only: the per-trait additive counts)
   const int rc = rg_s2_contract_packed(ctx, rows, ld, bs, rows_on_device, flip, &co);
+  ctx->contract_mask = nullptr;
   if (rc) return rc;
   bt.bs = bs; bt.kind = 1; bt.scale = 0;
   const int64_t Np = (ctx->n + 128 * RG_MAX_SEG - 1) / (128 * RG_MAX_SEG) * (128 * RG_MAX_SEG);
   bt.d_pk = (const uint8_t*)ctx->pbuf[RG_S2_Q_PK]; bt.ldp = Np / 4;       // the staged rows (flip applied, padding = 0 copies) stay for the corrections
   bt.d_g16 = nullptr; bt.ldg = 0;
   if (out->counts) memcpy(out->counts, counts.data(), sizeof(int32_t) * counts.size());
-  return score_from_sums(ctx, bs, numtol, counts.data(), nullptr, nullptr, 1, out);
+  if (ctx->coding == RG_S2_ADDITIVE) return score_from_sums(ctx, bs, numtol, counts.data(), nullptr, nullptr, 1, out);
+  // `--test dominant | recessive`: the staged rows were relabelled after k_s2_rows counted them, so the statistics are functions of the counts of the
+  // relabelled row (calls equal to 1: n1 + n2 or n2; none equal to 2, so flip_geno's verdict is never taken: Data.cpp:2108 turns it off); what is
+  // reported per trait stays additive (update_trait_counts runs before the recoding)
+  std::vector<int32_t> rcounts((size_t)bs * 4, 0);
+  for (int j = 0; j < bs; ++j) {
+    rcounts[(size_t)j * 4] = ctx->coding == RG_S2_DOMINANT ? counts[(size_t)j * 4] + counts[(size_t)j * 4 + 1] : counts[(size_t)j * 4 + 1];
+    rcounts[(size_t)j * 4 + 2] = counts[(size_t)j * 4 + 2];
+  }
+  const int rc2 = score_from_sums(ctx, bs, numtol, rcounts.data(), nullptr, nullptr, 1, out, counts.data());
+  if (rc2) return rc2;
+  if ((out->total_p || out->n_obs_p) && all_observed) {
+    for (size_t e = 0; e < (size_t)bs * P; ++e) { if (out->total_p) out->total_p[e] = 0.0; if (out->n_obs_p) out->n_obs_p[e] = 0; }
+  } else if (out->total_p || out->n_obs_p) {
+    std::vector<int32_t> tc;
+    const int rc3 = rg_s2_fetch_trait_counts(ctx, bs, tc);
+    if (rc3) return rc3;
+    for (int j = 0; j < bs; ++j) {
+      const int32_t tot = counts[(size_t)j * 4] + 2 * counts[(size_t)j * 4 + 1], nobs = (int32_t)ctx->n - counts[(size_t)j * 4 + 2];
+      for (int q = 0; q < P; ++q) {
+        const size_t e = (size_t)j * P + q;
+        if (out->total_p) out->total_p[e] = (double)(tc[2 * e] - tot);
+        if (out->n_obs_p) out->n_obs_p[e] = tc[2 * e + 1] - nobs;
+      }
+    }
+  }
+  return RG_S2_OK;
 }
 
 int rg_s2_bt_score_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int32_t scale, double numtol,

@@ -86,6 +86,13 @@ struct rg_s2_ctx {
   } last_qt;
   void* mbuf[4] = {nullptr, nullptr, nullptr, nullptr};      // rg_s2_qt_moments: listed rows, partial sums, b, results
   size_t mcap[4] = {0, 0, 0, 0};
+  // ---- rg_s2_set_coding (`--test dominant | recessive`): the staged hard-call rows are relabelled after they have been counted ----
+  int coding = RG_S2_ADDITIVE;
+  int staged_bs = 0;            // rows of the block last staged by a hard-call entry (rg_s2_packed_counts)
+  int32_t* d_tcnt = nullptr;    // [bs][P][2] additive allele count and observed samples per trait, taken before the relabelling
+  size_t tcnt_cap = 0;
+  bool tcnt_valid = false;
+  const uint8_t* contract_mask = nullptr;      // set by rg_s2_bt_score_packed around its rg_s2_contract_packed call: the traits' device masks
 };
 
 
@@ -114,5 +121,16 @@ static inline int rg_s2_ensure_in(rg_s2_ctx* ctx, void** buf, size_t* cap, int s
 enum { RG_S2_Q_PK = 0, RG_S2_Q_CNT = 1, RG_S2_Q_S = 2, RG_S2_Q_A = 3, RG_S2_Q_VAR = 4 };
 // slot of rg_s2_ctx::buf holding the uint16 dosage rows of the block handed to the integer-dosage entries from the host
 enum { RG_S2_B_G = 0 };
+// step2_qt.hip, non-additive codings only: after k_s2_rows has counted the staged rows, the per-trait additive counts against the device mask
+// [P][n] (null: none) and the relabelling of the rows in place; vstat (null: not wanted) is rewritten for the recoded row
+int rg_s2_apply_coding(rg_s2_ctx* ctx, uint8_t* pk, int64_t ldp, int bs, const int32_t* cnt, double* vstat, const uint8_t* dmask);
+// [bs][P][2] of the block last staged (inline: step2_bt.hip is also built on its own, against host stand-ins of the contraction entries)
+static inline int rg_s2_fetch_trait_counts(rg_s2_ctx* ctx, int bs, std::vector<int32_t>& out) {
+  if (!ctx->tcnt_valid || bs != ctx->staged_bs) return rg_s2_fail(ctx, RG_S2_ERR_ARG, "per-trait counts of the staged block are not there");
+  out.resize((size_t)bs * ctx->P * 2);
+  S2_HIP(hipMemcpyAsync(out.data(), ctx->d_tcnt, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+  S2_HIP(hipStreamSynchronize(ctx->st));
+  return RG_S2_OK;
+}
 void rg_s2_bt_free(rg_s2_ctx* ctx);   // step2_bt.hip
 void rg_s2_mcc_free(rg_s2_ctx* ctx);  // step2_mcc.hip

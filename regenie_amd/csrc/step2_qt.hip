@@ -419,6 +419,68 @@ __global__ __launch_bounds__(256) void k_s2_rows(uint8_t* __restrict__ pk, int64
   }
 }
 
+// ---- `--test dominant | recessive` (rg_s2_set_coding): launched for a non-additive coding only, between k_s2_rows and the contractions ----
+// Additive per-trait counts of a staged row BEFORE it is relabelled (update_trait_counts, Geno.cpp:2948-2959, runs before the recoding):
+// grid (bs, P); tc [bs][P][2] = allele count and observed samples among the samples trait p is observed for.  The padding codes (0 copies)
+// lie at positions >= n and are not read.
+__global__ __launch_bounds__(256) void k_s2_trait_counts(const uint8_t* __restrict__ pk, int64_t ldp, const uint8_t* __restrict__ M, int64_t n,
+                                                         int P, int32_t* __restrict__ tc) {
+  __shared__ int red[2][4];
+  const int j = blockIdx.x, p = blockIdx.y;
+  const uint8_t* row = pk + (int64_t)j * ldp;
+  const uint8_t* m = M + (int64_t)p * n;
+  const int64_t nbytes = (n + 3) / 4;
+  int tot = 0, nobs = 0;
+  for (int64_t b = threadIdx.x; b < nbytes; b += 256) {
+    const unsigned x = row[b];
+    const int64_t s0 = b * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (s0 + k < n && m[s0 + k]) {
+        const unsigned code = (x >> (2 * k)) & 3u;      // 00 -> 2 copies, 01 -> missing, 10 -> 1, 11 -> 0
+        tot += code == 0u ? 2 : (code == 2u ? 1 : 0);
+        nobs += code != 1u ? 1 : 0;
+      }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { tot += __shfl_down(tot, o); nobs += __shfl_down(nobs, o); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = tot; red[1][threadIdx.x >> 6] = nobs; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t* o = tc + ((int64_t)j * P + p) * 2;
+    o[0] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    o[1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+  }
+}
+
+// The relabelling of a staged row in place, one workgroup per row (parseSnpfromBed, Geno.cpp:2509-2515):
+//   CODING 1, dominant:  2 -> 1           code 00 -> 10                      hi' = hi | (~hi & ~lo)
+//   CODING 2, recessive: 1 -> 0, 2 -> 1   codes 10 -> 11, 00 -> 10           lo' = lo | hi, hi' = hi | ~lo
+// 01 (missing) and 11 (0 copies; the padding) stay.  cnt [bs][4] are k_s2_rows' ADDITIVE counts and stay as they are; vstat (sum, sum of
+// squares, observed, observed non-zero of the RECODED row, whose calls are 0 / 1) is rewritten from them.  pgen_zeros: the .pgen form of
+// check_sparse_G's rule counts the additive zeros while reading (Geno.cpp:2582-2594), so the non-zero count stays the additive one.
+template <int CODING>
+__global__ __launch_bounds__(256) void k_s2_recode(uint8_t* __restrict__ pk, int64_t ldp, int64_t n, const int32_t* __restrict__ cnt,
+                                                   double* __restrict__ vstat, int pgen_zeros) {
+  uint32_t* w = reinterpret_cast<uint32_t*>(pk + (int64_t)blockIdx.x * ldp);
+  const int64_t nwords = ldp / 4;
+  for (int64_t i = threadIdx.x; i < nwords; i += 256) {
+    const uint32_t x = w[i];
+    const uint32_t lo = x & 0x55555555u, hi = (x >> 1) & 0x55555555u;
+    uint32_t lo2, hi2;
+    if (CODING == 1) { lo2 = lo; hi2 = hi | (~hi & ~lo & 0x55555555u); }
+    else { lo2 = lo | hi; hi2 = (hi | ~lo) & 0x55555555u; }
+    const uint32_t y = lo2 | (hi2 << 1);
+    if (y != x) w[i] = y;
+  }
+  if (threadIdx.x == 0 && vstat) {
+    const int a = cnt[blockIdx.x * 4 + 0], b = cnt[blockIdx.x * 4 + 1], m = cnt[blockIdx.x * 4 + 2];
+    const int s = CODING == 1 ? a + b : b;      // calls equal to 1 after the relabelling
+    double* vs = vstat + (int64_t)blockIdx.x * 4;
+    vs[0] = (double)s; vs[1] = (double)s; vs[2] = (double)(n - m); vs[3] = (double)(pgen_zeros ? a + b : s);
+  }
+}
+
 // YtX[p][c] = sum_i res_p(i) x_c(i); grid (P * C), 256 threads, fixed summation tree
 __global__ __launch_bounds__(256) void k_s2_ytx(const double* __restrict__ X, const double* __restrict__ Y, int64_t n, int C, double* __restrict__ ytx) {
   __shared__ double red[4];
@@ -1175,7 +1237,46 @@ int ensure_lists(rg_s2_ctx* ctx) {
 int ensure_p(rg_s2_ctx* ctx, int slot, size_t bytes) { return ensure_in(ctx, ctx->pbuf, ctx->pcap, slot, bytes); }
 }  // namespace
 
+int rg_s2_apply_coding(rg_s2_ctx* ctx, uint8_t* pk, int64_t ldp, int bs, const int32_t* cnt, double* vstat, const uint8_t* dmask) {
+  ctx->tcnt_valid = false;
+  if (dmask) {
+    const size_t need = (size_t)bs * ctx->P * 2 * sizeof(int32_t);
+    if (ctx->tcnt_cap < need) {
+      if (ctx->d_tcnt) S2_HIP(hipFree(ctx->d_tcnt));
+      ctx->d_tcnt = nullptr; ctx->tcnt_cap = 0;
+      S2_HIP(hipMalloc((void**)&ctx->d_tcnt, need));
+      ctx->tcnt_cap = need;
+    }
+    hipLaunchKernelGGL(k_s2_trait_counts, dim3(bs, ctx->P), dim3(256), 0, ctx->st, (const uint8_t*)pk, ldp, dmask, ctx->n, ctx->P, ctx->d_tcnt);
+    ctx->tcnt_valid = true;
+  }
+  if (ctx->coding == RG_S2_DOMINANT)
+    hipLaunchKernelGGL(k_s2_recode<1>, dim3(bs), dim3(256), 0, ctx->st, pk, ldp, ctx->n, cnt, vstat, ctx->rule_zero_count);
+  else
+    hipLaunchKernelGGL(k_s2_recode<2>, dim3(bs), dim3(256), 0, ctx->st, pk, ldp, ctx->n, cnt, vstat, ctx->rule_zero_count);
+  S2_HIP(hipGetLastError());
+  return RG_S2_OK;
+}
+
 extern "C" {
+
+int rg_s2_set_coding(rg_s2_ctx* ctx, int32_t coding) {
+  if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_coding: context was not created");
+  if (coding != RG_S2_ADDITIVE && coding != RG_S2_DOMINANT && coding != RG_S2_RECESSIVE)
+    return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_coding: coding must be RG_S2_ADDITIVE, RG_S2_DOMINANT or RG_S2_RECESSIVE");
+  ctx->coding = coding;
+  ctx->last_qt.kind = 0;      // a scored block belongs to the coding it was scored under
+  return RG_S2_OK;
+}
+
+int rg_s2_packed_counts(rg_s2_ctx* ctx, int32_t* counts) {
+  if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_packed_counts: context was not created");
+  if (!counts || ctx->staged_bs < 1 || !ctx->pbuf[RG_S2_Q_CNT]) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_packed_counts: no hard-call block has been staged");
+  S2_HIP(hipSetDevice(ctx->dev));
+  S2_HIP(hipMemcpyAsync(counts, ctx->pbuf[RG_S2_Q_CNT], sizeof(int32_t) * 4 * (size_t)ctx->staged_bs, hipMemcpyDeviceToHost, ctx->st));
+  S2_HIP(hipStreamSynchronize(ctx->st));
+  return RG_S2_OK;
+}
 
 int rg_s2_create(rg_s2_ctx** out, int device, int64_t n, int32_t n_cov, int32_t n_pheno) {
   if (!out) return RG_S2_ERR_ARG;
@@ -1236,6 +1337,7 @@ void rg_s2_destroy(rg_s2_ctx* ctx) {
     if (ctx->dY) (void)hipFree(ctx->dY);
     if (ctx->dM) (void)hipFree(ctx->dM);
     if (ctx->dscf) (void)hipFree(ctx->dscf);
+    if (ctx->d_tcnt) (void)hipFree(ctx->d_tcnt);
     rg_s2_bt_free(ctx);
     rg_s2_mcc_free(ctx);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
@@ -1420,6 +1522,8 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   S2_HIP(hipMemcpy2DAsync(pk, ldp, rows, ld, nbytes, bs, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
   S2_HIP(hipEventRecord(ctx->e0, ctx->st));
   hipLaunchKernelGGL(k_s2_rows, dim3(bs), dim3(256), 0, ctx->st, pk, ldp, n, flip ? 1 : 0, cnt, total_miss, vstat);
+  ctx->staged_bs = bs;
+  if (ctx->coding != RG_S2_ADDITIVE && (rc = rg_s2_apply_coding(ctx, pk, ldp, bs, cnt, vstat, ((out->total_p || out->n_obs_p) && !ctx->complete) ? ctx->dM : nullptr))) return rc;      // (complete masks: every trait's counts are the variant's)
   // a block with a missing call contracts both sets (allele count, missing indicator) in one pass over the rows; the count comes back
   // from k_s2_rows first (4 bytes, one stream synchronisation: tens of microseconds against the milliseconds of the contraction)
   int32_t h_miss = 0;
@@ -1489,14 +1593,29 @@ int rg_s2_qt_block_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   if (out->mean) S2_HIP(hipMemcpyAsync(out->mean, mu, sizeof(double) * bs, hipMemcpyDeviceToHost, ctx->st));
   if (out->n_obs) S2_HIP(hipMemcpyAsync(out->n_obs, nobs, sizeof(int32_t) * bs, hipMemcpyDeviceToHost, ctx->st));
   if (out->ignored) S2_HIP(hipMemcpyAsync(out->ignored, ign, sizeof(int32_t) * bs, hipMemcpyDeviceToHost, ctx->st));
-  if (out->total_p) S2_HIP(hipMemcpyAsync(out->total_p, total_p, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
-  if (out->n_obs_p) S2_HIP(hipMemcpyAsync(out->n_obs_p, nobs_p, sizeof(int32_t) * bs * P, hipMemcpyDeviceToHost, ctx->st));
+  const bool coded = ctx->coding != RG_S2_ADDITIVE;       // total_p / n_obs_p are then the additive counts taken before the relabelling (below)
+  if (out->total_p && !coded) S2_HIP(hipMemcpyAsync(out->total_p, total_p, sizeof(double) * bs * P, hipMemcpyDeviceToHost, ctx->st));
+  if (out->n_obs_p && !coded) S2_HIP(hipMemcpyAsync(out->n_obs_p, nobs_p, sizeof(int32_t) * bs * P, hipMemcpyDeviceToHost, ctx->st));
   std::vector<int32_t> h_recheck(masked ? bs : 0);
   if (masked) S2_HIP(hipMemcpyAsync(h_recheck.data(), recheck, sizeof(int32_t) * bs, hipMemcpyDeviceToHost, ctx->st));
   S2_HIP(hipStreamSynchronize(ctx->st));
   float ms = 0.f;
   S2_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
   ctx->last_ms = ms;
+  if (coded && (out->total_p || out->n_obs_p)) {
+    std::vector<int32_t> tc;
+    if (ctx->complete) {
+      std::vector<int32_t> hc((size_t)bs * 4);
+      S2_HIP(hipMemcpy(hc.data(), cnt, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost));
+      tc.resize((size_t)bs * P * 2);
+      for (int j = 0; j < bs; ++j)
+        for (int p = 0; p < P; ++p) { tc[((size_t)j * P + p) * 2] = hc[(size_t)j * 4] + 2 * hc[(size_t)j * 4 + 1]; tc[((size_t)j * P + p) * 2 + 1] = (int32_t)n - hc[(size_t)j * 4 + 2]; }
+    } else if ((rc = rg_s2_fetch_trait_counts(ctx, bs, tc))) return rc;
+    for (size_t e = 0; e < (size_t)bs * P; ++e) {
+      if (out->total_p) out->total_p[e] = (double)tc[2 * e];
+      if (out->n_obs_p) out->n_obs_p[e] = tc[2 * e + 1];
+    }
+  }
   // The flagged variants (rare: a dense variant almost in the span of X) once more through rg_s2_qt_block, which forms the residual
   // g~ - X beta itself and sums mask_p r^2 over it: their staged rows (flip applied) come back, are decoded on the host and go in as fp64.
   std::vector<int32_t> redo;
@@ -1537,6 +1656,7 @@ int rg_s2_qt_block_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   if (!G || !out || bs < 1 || ld < n || scale < 1 || scale > 16384)
     return fail(ctx, RG_S2_ERR_ARG, "rg_s2_qt_block_int: bad arguments (need bs >= 1, ld >= n, 1 <= scale <= 16384)");
   const int C = ctx->C, P = ctx->P, Cv = C + P;
+  ctx->staged_bs = 0;      // the counts buffer of a staged hard-call block is reused below
   S2_HIP(hipSetDevice(ctx->dev));
   int rc;
   if ((rc = ensure_planes(ctx, ctx->planes_mask_cols))) return rc;       // [X | res] lead the planes whatever else they hold
@@ -1701,6 +1821,8 @@ int rg_s2_contract_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32
   S2_HIP(hipMemcpy2DAsync(pk, ldp, rows, ld, nbytes, bs, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
   S2_HIP(hipEventRecord(ctx->e0, ctx->st));
   hipLaunchKernelGGL(k_s2_rows, dim3(bs), dim3(256), 0, ctx->st, pk, ldp, n, flip ? 1 : 0, cnt, total_miss, (double*)nullptr);
+  ctx->staged_bs = bs;
+  if (ctx->coding != RG_S2_ADDITIVE && (rc = rg_s2_apply_coding(ctx, pk, ldp, bs, cnt, nullptr, ctx->contract_mask))) return rc;
   int32_t h_miss = 0;      // as in rg_s2_qt_block_packed: both sets in one pass when the block has a missing call
   S2_HIP(hipMemcpyAsync(&h_miss, total_miss, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
   S2_HIP(hipStreamSynchronize(ctx->st));
@@ -1732,6 +1854,7 @@ int rg_s2_contract_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs
   const int64_t n = ctx->n;
   if (!G || !out || bs < 1 || ld < n || scale < 1 || scale > 16384)
     return fail(ctx, RG_S2_ERR_ARG, "rg_s2_contract_int: bad arguments (need bs >= 1, ld >= n, 1 <= scale <= 16384)");
+  ctx->staged_bs = 0;      // the counts buffer of a staged hard-call block is reused below
   S2_HIP(hipSetDevice(ctx->dev));
   const int ncol = ctx->g_ncol, nsq = ctx->g_nsq, ngrp = (ncol + 15) / 16;
   const int64_t Np = (n + 128 * RG_MAX_SEG - 1) / (128 * RG_MAX_SEG) * (128 * RG_MAX_SEG);

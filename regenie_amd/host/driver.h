@@ -124,6 +124,12 @@ struct Params {
   // :1262-1277; compute_score_qt_mcc, Step2_Models.cpp:237-341)
   bool mcc = false;
   double mcc_thr = 0.01, mcc_skew = 0.0;
+  // --step 2 --test additive|dominant|recessive [--minHOMs N] (Regenie.cpp:282, :735-740, :906-907): the genotype coding of the single-variant tests
+  // (params.test_type 0 / 1 / 2 = RG_S2_ADDITIVE / RG_S2_DOMINANT / RG_S2_RECESSIVE of include/rg_step2.h); the recessive test ignores a variant whose
+  // recoded sum over the observed samples -- the homALT carriers -- is below --minHOMs (Geno.cpp:2517-2521)
+  int test_type = 0;
+  bool saw_test = false;
+  double min_homs = 0.0;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards

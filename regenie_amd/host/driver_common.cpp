@@ -356,6 +356,20 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--mcc") p.mcc = true;
     else if (a == "--mcc-thr") p.mcc_thr = atof(need(i).c_str());
     else if (a == "--mcc-skew") p.mcc_skew = atof(need(i).c_str());
+    else if (a == "--test") {                                                                // Regenie.cpp:735-740
+      const std::string v = need(i);
+      p.saw_test = true;
+      if (v == "additive") p.test_type = 0;
+      else if (v == "dominant") p.test_type = 1;
+      else if (v == "recessive") p.test_type = 2;
+      else usage_error("unrecognized argument for option --test, must be either 'additive', 'dominant' or 'recessive'.");
+    }
+    else if (a == "--minHOMs") {                                                             // Regenie.cpp:282 (a FLOAT, default 0, no range check)
+      const std::string v = need(i);
+      char* end = nullptr;
+      p.min_homs = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != '\0') usage_error("Argument \u2018" + v + "\u2019 failed to parse");      // the option parser's own message
+    }
     else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
     else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
     else if (a == "--forcein-vars") p.forcein_vars = true;
@@ -439,6 +453,8 @@ Params parse_args(int argc, char** argv) {
     if (p.forcein_vars && p.extract.size() > 1) usage_error("cannot have multiple extract files");      // Geno.cpp:1352
     p.forcein_vars = p.forcein_vars && !p.extract.empty();
   }
+  if (p.saw_test && p.step != 2) usage_error("can only use --test in step 2 (association testing).");      // Regenie.cpp:906-907
+  if (p.test_type > 0 && p.compute_corr) usage_error("--test dominant / recessive with --compute-corr (the LD matrix of recoded genotypes) is not built.");
   if (p.ld_dosages && !p.compute_corr) usage_error("--ld-dosages goes with --compute-corr / --output-corr-text.");
   if (p.step == 2 && !p.compute_corr) {
     if (p.pred_list.empty()) usage_error("option '--pred' is required (use the _pred.list file written by step 1).");

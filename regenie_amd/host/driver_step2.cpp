@@ -27,6 +27,8 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p)
   show_info = r.dosage_mode;                            // params.dosage_mode: the INFO column
   flip = (in == In::Bed && p.ref_first) ? 1 : 0;        // .pgen rows always count ALT (PgenReader::Read / ReadHardcalls)
   dscale = r.bgenh ? 255 : 16384;
+  coding = p.test_type;
+  test_name = coding == 1 ? "DOM" : coding == 2 ? "REC" : "ADD";
   multi = part.nparts > 1;                              // parts write plain part files; run_step2_all concatenates (and compresses) them
   for (size_t j = 0; j < r.snp_chrom.size(); ++j) chr_snps[r.snp_chrom[j]].push_back((int64_t)j);
   for (auto& kv : chr_snps) total_blocks += (int)((kv.second.size() + p.bsize - 1) / p.bsize);
@@ -272,7 +274,8 @@ struct BlockCounts {
   std::vector<double> total, info_num, af_t, info_t;
   std::vector<int64_t> ns1, ns_t;
   std::vector<uint8_t> variant_ignored;
-  explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0) {}
+  std::vector<double> sum_pos;      // --test dominant | recessive: the recoded vector's sum over the observed samples (the counts above stay additive)
+  explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0), sum_pos(bs, 0.0) {}
 };
 
 // One block through the tests: an input route leaves the counts and the genotype source, the scorer the statistics, correct() the
@@ -287,7 +290,7 @@ struct S2Block {
   int bs = 0;
   std::vector<int64_t> vidx;                        // the block's variants in the file
   std::vector<uint8_t> rows_buf, packed;
-  std::vector<double> dbuf, ibuf, G;
+  std::vector<double> dbuf, ibuf, cbuf, G;
   std::vector<uint16_t> G16;
   // the source an input route leaves for the scorer: 2-bit rows (hard calls), uint16 rows (integral) or the doubles of G
   const uint8_t* rows = nullptr; int64_t ld = 0;
@@ -318,7 +321,11 @@ struct S2Block {
     dbuf.resize((size_t)bs * r.n_file);
     if (r.bgenh) {            // parseSnpfromBGEN (Geno.cpp:2186-2330): dosages and the terms of the IMPUTE info score
       ibuf.resize((size_t)bs * r.n_file);
-      if (rg_bgen_read_dosages_info(r.bgenh, bs, vidx.data(), cm.p.ref_first ? 1 : 0, dbuf.data(), ibuf.data(), r.n_file) != RG_BGEN_OK)
+      if (cm.coding) {        // its second pass too (Geno.cpp:2362-2392): the coded probabilities the test takes
+        cbuf.resize((size_t)bs * r.n_file);
+        if (rg_bgen_read_dosages_coded(r.bgenh, bs, vidx.data(), cm.p.ref_first ? 1 : 0, cm.coding, dbuf.data(), ibuf.data(), cbuf.data(), r.n_file) != RG_BGEN_OK)
+          throw std::runtime_error(rg_bgen_last_error(r.bgenh));
+      } else if (rg_bgen_read_dosages_info(r.bgenh, bs, vidx.data(), cm.p.ref_first ? 1 : 0, dbuf.data(), ibuf.data(), r.n_file) != RG_BGEN_OK)
         throw std::runtime_error(rg_bgen_last_error(r.bgenh));
     } else if (rg_pgen_read_dosage_rows(r.pgen, bs, vidx.data(), dbuf.data(), r.n_file) != RG_PGEN_OK)   // Read() (Geno.cpp:2570-2571)
       throw std::runtime_error(rg_pgen_last_error(r.pgen));
@@ -330,6 +337,7 @@ struct S2Block {
     bc.total.assign(pb.total, pb.total + bs); bc.ns1.assign(pb.ns1, pb.ns1 + bs);
     bc.info_num.assign(pb.info_num, pb.info_num + bs);
     bc.variant_ignored.assign(pb.ignored, pb.ignored + bs);
+    if (cm.coding) bc.sum_pos.assign(pb.sum_pos, pb.sum_pos + bs);
     if (cm.per_trait) { bc.af_t.assign(pb.af_t, pb.af_t + bs * P); bc.ns_t.assign(pb.ns_t, pb.ns_t + bs * P); bc.info_t.assign(pb.info_t, pb.info_t + bs * P); }
     integral = true; g16p = pb.g16; g16ld = pb.ld; g16_on_device = pb.on_device;
   }
@@ -346,18 +354,23 @@ struct S2Block {
     parallel_for(bs, cm.nthreads, [&](int j) {
       const double* d = dbuf.data() + (size_t)j * r.n_file;
       const double* iv = r.bgenh ? ibuf.data() + (size_t)j * r.n_file : nullptr;
+      const double* cv = (cm.coding && r.bgenh) ? cbuf.data() + (size_t)j * r.n_file : nullptr;
       double* g = G.data() + (size_t)j * n;
-      double tot = 0.0, inf = 0.0; int64_t ns = 0;
+      double tot = 0.0, inf = 0.0, pos = 0.0; int64_t ns = 0;
       for (int64_t k = 0; k < n; ++k) {
         const int64_t i = cm.file_idx[k];
         const double v = d[i];
         g[k] = v;
         if (v == -3.0) continue;
+        if (cm.coding) {      // the vector the test takes: the coded BGEN probabilities (.pgen dosage tracks are refused in run_step2)
+          g[k] = cv[i];
+          pos += g[k];
+        }
         const double e = iv ? iv[i] : v * v;
         tot += v; inf += e; ++ns;
         if (cm.per_trait && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, v, e, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], &bc.info_t[(size_t)j * P]);
       }
-      bc.total[j] = tot; bc.ns1[j] = ns; bc.info_num[j] = inf;
+      bc.total[j] = tot; bc.ns1[j] = ns; bc.info_num[j] = inf; bc.sum_pos[j] = pos;
       if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
     });
     // 8-bit .bgen probabilities and .pgen dosages are integers in units of 1 / 255 and 1 / 16384: as uint16 rows they take the
@@ -399,20 +412,31 @@ struct S2Block {
     parallel_for(bs, cm.nthreads, [&](int j) {
       const uint8_t* row = rows + (size_t)j * cm.r.bpr;
       double* g = G.data() + (size_t)j * n;
-      double tot = 0.0; int64_t ns = 0;
+      double tot = 0.0, pos = 0.0; int64_t ns = 0;
       for (int64_t k = 0; k < n; ++k) {
         const int64_t i = cm.file_idx[k];
         double hc = lut[(row[i >> 2] >> (2 * (i & 3))) & 3];
         if (flip && hc != -3.0) hc = 2.0 - hc;
         g[k] = hc;
         if (hc != -3.0) {
+          if (cm.coding) { g[k] = recode_hard_call(hc, cm.coding); pos += g[k]; }
           tot += hc; ++ns;
           if (cm.any_missing && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, hc, 0.0, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], nullptr);
         }
       }
-      bc.total[j] = tot; bc.ns1[j] = ns;
+      bc.total[j] = tot; bc.ns1[j] = ns; bc.sum_pos[j] = pos;
       if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
     });
+  }
+
+  // --test dominant | recessive, after the additive filters (parseSnpfromBed, Geno.cpp:2517-2527, and its like in every reader): the recessive test
+  // ignores a variant with fewer than --minHOMs homALT carriers (the recoded sum), both a variant whose recoded mean is below numtol
+  void coding_filters(BlockCounts& bc) const {
+    if (!cm.coding) return;
+    for (int j = 0; j < bs; ++j) {
+      if (cm.coding == 2 && bc.sum_pos[j] < cm.p.min_homs) bc.variant_ignored[j] = 1;
+      if (bc.ns1[j] > 0 && bc.sum_pos[j] / (double)bc.ns1[j] < NUMTOL) bc.variant_ignored[j] = 1;
+    }
   }
 
   // quantitative traits: the block's statistics from whatever source the route left
@@ -422,8 +446,15 @@ struct S2Block {
     memset(&o, 0, sizeof(o));
     o.stats = stats.data(); o.bhat = bhat.data(); o.scale_fac = sfac.data(); o.ignored = ign.data();
     if (cm.in == In::Dosage) {
-      if (integral) check(rg_s2_qt_block_int(s2, g16p, g16ld, bs, g16_on_device, cm.dscale, NUMTOL, &o));
-      else check(rg_s2_qt_block(s2, G.data(), cm.n, bs, 0, NUMTOL, &o));
+      std::vector<double> mean_c(cm.coding ? bs : 0);
+      std::vector<int32_t> nobs_c(cm.coding ? bs : 0);
+      if (cm.coding && integral) { o.mean = mean_c.data(); o.n_obs = nobs_c.data(); }
+      if (!integral) { check(rg_s2_qt_block(s2, G.data(), cm.n, bs, 0, NUMTOL, &o)); return; }
+      check(rg_s2_qt_block_int(s2, g16p, g16ld, bs, g16_on_device, cm.dscale, NUMTOL, &o));
+      // rows the device decoder coded: their sum is an integer in units of 1 / scale, recovered exactly from the mean the entry returns
+      for (int j = 0; cm.coding && j < bs; ++j) {
+        if (std::isnan(bc.sum_pos[j])) bc.sum_pos[j] = std::nearbyint(mean_c[j] * (double)nobs_c[j] * cm.dscale) / cm.dscale;
+      }
       return;
     }
     if (cm.env.dense) { check(rg_s2_qt_block(s2, G.data(), cm.n, bs, 0, NUMTOL, &o)); return; }
@@ -435,9 +466,15 @@ struct S2Block {
       o.total_p = totp_v.data(); o.n_obs_p = nobsp_v.data();
     }
     check(rg_s2_qt_block_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &o));
+    std::vector<int32_t> cnt_v;      // --test dominant | recessive: the mean is the recoded vector's, the additive counts come on their own
+    if (cm.coding) { cnt_v.resize((size_t)bs * 4); check(rg_s2_packed_counts(s2, cnt_v.data())); }
     if (cm.any_missing) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); }
     for (int j = 0; j < bs; ++j) {
       bc.ns1[j] = nobs_v[j];
+      if (cm.coding) {
+        const double n1 = cnt_v[(size_t)j * 4], n2 = cnt_v[(size_t)j * 4 + 1];
+        bc.total[j] = n1 + 2.0 * n2; bc.sum_pos[j] = cm.coding == 1 ? n1 + n2 : n2;
+      } else
       bc.total[j] = std::nearbyint(mean_v[j] * (double)nobs_v[j]);       // the allele count is an integer: mean = total / n_obs
       if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
       if (cm.any_missing)                                                  // update_trait_counts (Geno.cpp:2948-2959) as differences from the totals
@@ -511,6 +548,8 @@ struct S2Block {
       if (!integral) throw std::runtime_error("--step 2 --bt / --ct on dosages that are not integer multiples of 1/" + std::to_string(cm.dscale) + " is not built.");
       bo.vstat = bt_vstat.data();
       check(rg_s2_bt_score_int(s2, g16p, g16ld, bs, g16_on_device, cm.dscale, NUMTOL, &bo));
+      for (int j = 0; cm.coding && j < bs; ++j)      // rows the device decoder coded: vstat[0] is their exact integer sum
+        if (std::isnan(bc.sum_pos[j])) bc.sum_pos[j] = bt_vstat[(size_t)j * 4] / cm.dscale;
     } else {
       bo.counts = bt_counts.data(); bo.total_p = totp.data(); bo.n_obs_p = nobsp.data();
       check(rg_s2_bt_score_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &bo));
@@ -520,7 +559,8 @@ struct S2Block {
     for (int j = 0; j < bs; ++j) {
       if (!dosage) {
         const double n1 = bt_counts[(size_t)j * 4], n2 = bt_counts[(size_t)j * 4 + 1], nm = bt_counts[(size_t)j * 4 + 2];
-        bc.ns1[j] = (int64_t)((double)cm.n - nm); bc.total[j] = n1 + 2.0 * n2;
+        bc.ns1[j] = (int64_t)((double)cm.n - nm); bc.total[j] = n1 + 2.0 * n2;      // (the counts are additive under every coding)
+        if (cm.coding) bc.sum_pos[j] = cm.coding == 1 ? n1 + n2 : n2;
       }
       sfac[j] = 1.0;
       if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
@@ -573,7 +613,7 @@ struct S2Block {
         for (int64_t k = 0; k < n; ++k) {
           double hc = lut[(row[k >> 2] >> (2 * (k & 3))) & 3];
           if (cm.flip && hc != -3.0) hc = 2.0 - hc;
-          gt[k] = hc == -3.0 ? mu : hc;
+          gt[k] = hc == -3.0 ? mu : recode_hard_call(hc, cm.coding);      // (mu: the recoded vector's mean under --test dominant | recessive)
         }
       }
       // the exact test (fit_firth_logistic_snp, Step2_Models.cpp:1062-1156): design [covariates | g~ on its raw scale], offset = the LOCO
@@ -649,7 +689,7 @@ struct S2Block {
           if (af >= 0) ln << head.str() << af << " ";            // print_sum_stats_single (Step2_Models.cpp:2505-2518): a negative value is "NA"
           else ln << head.str() << "NA ";
           if (show_info) { if (info >= 0) ln << info << " "; else ln << "NA "; }      // (the IMPUTE score of very uncertain dosages can be negative)
-          ln << nsq << " ADD ";
+          ln << nsq << ' ' << cm.test_name << ' ';
           if (se >= 0 && !std::isnan(se)) ln << bh << ' ' << se;
           else ln << "NA NA";
           if (chisq >= 0 && !std::isnan(logp) && !test_fail) ln << ' ' << chisq << ' ' << logp;
@@ -671,12 +711,17 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
   const S2Common cm(r, part);
   const Params& p = cm.p;
   const int P = cm.P;
+  // The reference rounds a .pgen dosage track to hard calls under a coding (Geno.cpp:2669-2679) but keeps check_sparse_G's zero count of the ADDITIVE
+  // dosages (:2594); the integer-dosage entries count the zeros of the row they are given, so that combination is not built
+  if (cm.coding && cm.in == In::Dosage && !r.bgenh)
+    throw std::runtime_error("--test dominant / recessive on a .pgen file with dosages is not built: use hard calls (a .pgen without a dosage track, or --bed).");
   ChromNull null(cm);
   rg_s2_ctx* s2 = nullptr;
   if (rg_s2_create(&s2, part.device, cm.n, cm.C, P) != RG_S2_OK || !s2) throw std::runtime_error("no MI355X / HIP device available (rg_s2_create failed)");
   S2Block blk(cm, null, s2);
   // check_sparse_G: params.n_samples, params.prop_zero_thr (Regenie.hpp:311); the .pgen reader counts the observed zeros itself
   blk.check(rg_s2_set_sparse_rule(s2, cm.N, 0.5, r.pgen ? 1 : 0));
+  if (cm.coding) blk.check(rg_s2_set_coding(s2, cm.coding));      // (an additive run never calls it)
   // in_non_par (Geno.cpp:2419, :2251): outside the pseudo-autosomal regions of chromosome X the reference halves the males' calls in the
   // MAC (and, with the default dosage compensation off, nothing else) -- with no male in the sample file that is the autosomal rule
   if (cm.chr_snps.count(p.nchrom) && r.has_male)
@@ -686,6 +731,7 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
   sout << std::left << std::setw(20) << " * # blocks" << ": [" << cm.total_blocks << "]\n";
   sout << " * approximate memory usage : n/a (genotype blocks are tested on the GPU)\n";
   sout << " * using minimum MAC of " << p.min_mac << " (variants with lower MAC are ignored)\n";
+  if (cm.coding == 2 && p.min_homs > 0) sout << " * ignoring variants (masks for gene-based tests) with fewer than " << p.min_homs << " homALT carriers\n";      // Data.cpp:2059-2060
 
   // output files, one per phenotype (split_by_pheno is the default; print_header_output_single, Step2_Models.cpp:2386-2398)
   std::vector<std::unique_ptr<TextOut>> ofs;
@@ -738,6 +784,7 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
       else blk.from_dense_bed(bc);
       // score, correct, format
       if (cm.glm) blk.score_glm(bc); else blk.score_qt(bc);
+      blk.coding_filters(bc);
       if (cm.glm && cm.correct) blk.correct(bc);
       if (cm.mcc) blk.mcc(bc);
       auto t_fmt = std::chrono::steady_clock::now();

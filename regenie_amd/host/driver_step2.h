@@ -56,6 +56,14 @@ constexpr unsigned DOSAGE_NOT_INTEGRAL = 0x10000u;
 // (Geno.cpp:2286-2290).  Above 510 (prob0 + prob1 > 1 in the file) it is no dosage in [0, 2]; the value is returned as it is.
 inline unsigned bgen_dosage_255(unsigned b0, unsigned b1, bool ref_first) { return ref_first ? b1 + 2u * (b0 + b1 < 255u ? 255u - b0 - b1 : 0u) : b1 + 2u * b0; }
 inline bool bgen_dosage_integral(unsigned q) { return q <= 510u; }
+// `--test dominant | recessive` (coding 1 | 2), parseSnpfromBGEN's second pass (Geno.cpp:2384-2389), in units of 1 / 255: prob0 + prob1 | prob0, with
+// --ref-first prob1 + prob2 | prob2 (prob2 = max(1 - prob0 - prob1, 0)).  At most 255 in a file whose probabilities sum to at most 1.
+inline unsigned bgen_coded_255(unsigned b0, unsigned b1, bool ref_first, int coding) {
+  const unsigned b2 = b0 + b1 < 255u ? 255u - b0 - b1 : 0u;
+  return coding == 1 ? (ref_first ? b1 + b2 : b0 + b1) : (ref_first ? b2 : b0);
+}
+// the same relabelling of a hard call 0 / 1 / 2 (parseSnpfromBed, Geno.cpp:2511-2515; the .pgen reader rounds a dosage to a hard call first, :2672-2678)
+inline double recode_hard_call(double hc, int coding) { return coding == 1 ? (hc == 2.0 ? 1.0 : hc) : coding == 2 ? (hc >= 1.0 ? hc - 1.0 : hc) : hc; }
 // a .pgen dosage in units of 1 / 16384; -3 is the missing value
 inline unsigned pgen_dosage_16384(double g) {
   if (g == -3.0) return 0xFFFFu;
@@ -83,6 +91,8 @@ struct S2Common : SampleMap {
   double z_thr;
   In in;
   int flip, dscale, nthreads, nt_prep;
+  int coding;                                   // --test: 0 additive, 1 dominant, 2 recessive (= RG_S2_ADDITIVE / _DOMINANT / _RECESSIVE)
+  const char* test_name;                        // the TEST column: ADD / DOM / REC (Data.cpp:2077-2089)
   int64_t ld16;                                 // leading dimension of the host threads' uint16 dosage rows
 };
 
@@ -128,6 +138,7 @@ GroupPlan plan_groups(const std::vector<BlkRef>& blocks, int bsize, int dev_targ
 // what the read-ahead hands the block loop: a view of the block's rows in its prepared group (valid until the group after the next is started)
 struct PreparedBlock {
   const double *total, *info_num, *af_t, *info_t;       // the *_t: [bs][P], only with S2Common::per_trait
+  const double* sum_pos;                                // only with S2Common::coding: the recoded values' sum over the observed samples
   const int64_t *ns1, *ns_t;
   const uint8_t* ignored;
   const uint16_t* g16; int64_t ld; int on_device;
@@ -158,7 +169,7 @@ class BgenAhead {
   struct DosPrep {
     uint16_t* g16 = nullptr;                 // pinned, rows of ld16 entries
     std::vector<uint8_t> raw, ignored;
-    std::vector<double> total, info_num, af_t, info_t;
+    std::vector<double> total, info_num, af_t, info_t, sum_pos;
     std::vector<int64_t> ns1, ns_t;
     bool integral = false;
     double ms_inflate = 0, ms_walk = 0, ms_wall = 0;

@@ -48,12 +48,13 @@ BgenAhead::BgenAhead(const S2Common& cm) : cm_(cm) {
   block_bytes_ = (block_bytes_ + 63) / 64 * 64;
   int32_t bcomp = 0;
   rg_bgen_info(r.bgenh, nullptr, nullptr, &bcomp, nullptr);
-  // the device decoder: default for zlib files
+  // the device decoder: default for zlib files (under --test dominant | recessive its rows hold the coded probabilities, its sums stay additive)
   if (bcomp == 1 && !cm.env.bgen_host && rg_bgen_dev_create(&bdev_, cm.part.device) == RG_BGEN_OK) {
     if (rg_bgen_dev_set_samples(bdev_, r.n_file, cm.n, cm.identity ? nullptr : cm.file_idx.data(), cm.per_trait ? cm.P : 0, cm.per_trait ? cm.Mc.data() : nullptr) != RG_BGEN_OK) {
       rg_bgen_dev_destroy(bdev_);
       bdev_ = nullptr;
     }
+    if (bdev_ && cm.coding && rg_bgen_dev_set_coding(bdev_, cm.coding) != RG_BGEN_OK) { rg_bgen_dev_destroy(bdev_); bdev_ = nullptr; }
   }
   std::vector<BlkRef> my_blocks;             // this part's blocks in the order they are tested
   int b = 0;
@@ -108,6 +109,7 @@ const PreparedBlock* BgenAhead::next_block() {
   v.integral = d.integral;
   if (!d.integral) return &v;
   v.total = d.total.data() + r0; v.ns1 = d.ns1.data() + r0; v.info_num = d.info_num.data() + r0; v.ignored = d.ignored.data() + r0;
+  v.sum_pos = cm_.coding ? d.sum_pos.data() + r0 : nullptr;
   if (cm_.per_trait) { v.af_t = d.af_t.data() + r0 * P; v.ns_t = d.ns_t.data() + r0 * P; v.info_t = d.info_t.data() + r0 * P; }
   v.ld = on_dev ? d.ld_dev : cm_.ld16;
   v.g16 = on_dev ? d.g16_dev + r0 * (size_t)v.ld : d.g16 + (r0 - (size_t)d.host_row0) * (size_t)v.ld;
@@ -174,6 +176,7 @@ bool BgenAhead::prepare_dev(const BlkRef& br, DosPrep& d, int slot, int64_t gi, 
   for (int j = 0; j < bs; ++j) {
     // the walk's exact integer sums in the units the host route accumulates as doubles: dosages in 1 / 255, info terms in 1 / 65025
     d.total[j] = (double)sq[j] / 255.0; d.info_num[j] = (double)si[j] / 65025.0; d.ns1[j] = no[j];
+    if (cm_.coding) d.sum_pos[j] = NAN;      // the coded rows' sum comes back with their scores (S2Block::score_*)
     if (maxq[j] > 510) bad = true;
     const double mac = std::min(d.total[j], 2.0 * d.ns1[j] - d.total[j]);
     // The sum here is the exact integer sum / 255; the host route and regenie add the samples' doubles in order.  A count that lands on
@@ -203,6 +206,7 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
   const int64_t n = cm_.n, ld16 = cm_.ld16, block_bytes = block_bytes_;
   const bool per_trait = cm_.per_trait, identity = cm_.identity, rf = cm_.p.ref_first;
   const double min_mac = cm_.p.min_mac;
+  const int coding = cm_.coding;
   const int64_t* file_idx = cm_.file_idx.data();
   const uint8_t *has_missing = cm_.has_missing.data(), *Mc = cm_.Mc.data();
   if (lo >= bs) return;
@@ -226,7 +230,7 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
       const uint8_t* ploidy = blk + 8;
       const uint8_t* pr = blk + 10 + r.n_file;
       uint16_t* q16 = d.g16 + (size_t)(j - lo) * ld16;
-      double tot = 0.0, inf = 0.0; int64_t ns = 0;
+      double tot = 0.0, inf = 0.0, pos = 0.0; int64_t ns = 0;
       unsigned worst = 0;
       double* af_t = nullptr; int64_t* ns_t = nullptr; double* info_t = nullptr;
       if (per_trait) {
@@ -249,13 +253,18 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
           qi = bgen_dosage_255(b0, b1, false);
         }
         worst = std::max(worst, qi);
-        q16[k] = (uint16_t)qi;
+        if (coding) {      // the row the test takes: the coded probability (the sums stay those of the additive dosage)
+          q16[k] = (uint16_t)bgen_coded_255(b0, b1, rf, coding);
+          const double p2 = rf ? std::max(1.0 - p0 - p1, 0.0) : 0.0;
+          pos += coding == 1 ? (rf ? p1 + p2 : p0 + p1) : (rf ? p2 : p0);
+        } else q16[k] = (uint16_t)qi;
         tot += v; inf += e; ++ns;
         if (per_trait && has_missing[k]) subtract_masked(Mc, n, P, k, v, e, af_t, ns_t, info_t);
       }
       for (int64_t k = n; k < ld16; ++k) q16[k] = 0;
       if (!bgen_dosage_integral(worst)) d.host_bad = 1;          // prob0 + prob1 > 1 in the file: not a dosage in [0, 2], the general route reports what the reference would
       d.total[j] = tot; d.ns1[j] = ns; d.info_num[j] = inf;
+      if (coding) d.sum_pos[j] = pos;
       d.ignored[j] = below_min_mac(tot, (double)ns, min_mac) ? 1 : 0;
       auto t2 = std::chrono::steady_clock::now();
       d.w_inf[w] += std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -276,6 +285,7 @@ void BgenAhead::prepare(size_t gi) {
     d.vi.resize(bs);
     for (int j = 0; j < bs; ++j) d.vi[j] = cm_.r.snp_offset[(*br.snps)[br.j0 + j]];
     d.g16_dev = nullptr; d.ms_read = d.ms_dev = 0; d.dev_rows = 0; d.host_row0 = 0; d.dev_bad = false; d.host_bad = 0;
+    if (cm_.coding) d.sum_pos.assign(bs, 0.0);
     d.total.assign(bs, 0.0); d.info_num.assign(bs, 0.0); d.ns1.assign(bs, 0); d.ignored.assign(bs, 0);
     if (cm_.per_trait) { d.af_t.assign((size_t)bs * P, 0.0); d.ns_t.assign((size_t)bs * P, 0); d.info_t.assign((size_t)bs * P, 0.0); }
     d.w_inf.assign(nt_prep, 0.0); d.w_walk.assign(nt_prep, 0.0);

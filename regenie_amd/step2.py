@@ -41,6 +41,7 @@ class _MccOut(C.Structure):
 
 
 BT_FIRTH_APPROX, BT_SPA = 1, 2
+ADDITIVE, DOMINANT, RECESSIVE = 0, 1, 2      # rg_s2_set_coding
 
 
 class Step2QT:
@@ -90,6 +91,18 @@ class Step2QT:
         """check_sparse_G's constants (Geno.cpp:3165-3177): params.n_samples (kept samples of the file) and --prop-zero-thr;
         zero_count_rule = the .pgen form (observed zeros >= n_samples * thr)."""
         self._check(self.lib.rg_s2_set_sparse_rule(self.h, int(n_samples), float(prop_zero_thr), 1 if zero_count_rule else 0))
+
+    def set_coding(self, coding: int) -> None:
+        """`--test`: ADDITIVE (0, the default), DOMINANT (1: 2 -> 1) or RECESSIVE (2: 1 -> 0, 2 -> 1).  The hard-call entries (score_block_packed,
+        contract_packed, bt_score_packed) relabel the staged rows after counting them: statistics and mean are the recoded vector's, counts / total_p /
+        n_obs_p stay additive (include/rg_step2.h).  Integer dosages are taken as they come (regenie_amd.bgen writes the coded value)."""
+        self._check(self.lib.rg_s2_set_coding(self.h, int(coding)))
+
+    def packed_counts(self, bs: int) -> np.ndarray:
+        """Additive call counts [bs][4] (ones, twos, missing, 0) of the block last staged by a hard-call entry; bs = its rows."""
+        counts = np.zeros((int(bs), 4), np.int32)
+        self._check(self.lib.rg_s2_packed_counts(self.h, counts.ctypes.data))
+        return counts
 
     def score_block(self, G, numtol: float = NUMTOL) -> dict:
         """G: numpy [bs][n] float64 (host), or a CUDA torch tensor [bs][n] float64 (read in place).  Missing = NaN or < 0."""

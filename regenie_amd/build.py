@@ -72,6 +72,7 @@ def _lib_deps():
                                                       os.path.join(CSRC, "rg_internal.h"),
                                                       os.path.join(CSRC, "chol_common.h"),
                                                       os.path.join(CSRC, "chol_p128.h"),
+                                                      os.path.join(CSRC, "l1_stage.h"),
                                                       os.path.join(CSRC, "step2_internal.h"),
                                                       os.path.join(CSRC, "pgen_reader.h"),
                                                       os.path.join(CSRC, "bgen_reader.h"),

@@ -121,7 +121,6 @@ __global__ __launch_bounds__(256, 2) void k_l1_gram64(L1G64 g, SegLayout seg) {
 // Work items come from a host-built table: (macro row, macro column, fold, K slice), ordered so that the workgroups an XCD
 // holds at one time belong to one 4 x 4 super tile of one (fold, slice) and stream the same rows through that XCD's L2.
 // The y row (W_f^T y_f) is k_l1_wty's; multi-GPU: rank r computes the macro tiles with index = r (mod world).
-struct L1Item { int16_t mr, mc, fold, slice; };
 struct L1G128 {
   L1Rows R; int rtot, nslice; const L1Item* items; double* out; int64_t slice_stride;
 };
@@ -229,36 +228,6 @@ __global__ __launch_bounds__(256) void k_l1_wty(L1Rows R, SegLayout seg, int rto
   if (threadIdx.x == 0) out[(int64_t)f * rtot * R.n64 + (int64_t)R.n64 * R.n64 + l] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// Work table of k_l1_gram128 for one rank (see the kernel): macro tiles (mr >= mc) of the padded order n64, K folds, nslice K
-// slices.  Groups = the macro tiles of one 4 x 4 super tile of one (fold, slice); the groups are dealt to the eight XCDs and
-// workgroup id 8 j + x is the j-th item of XCD x's list (ids are dispatched to XCD id mod 8).  Lists are padded with fold = -1.
-static std::vector<L1Item> l1_build_items(int n64, int K, int nslice, int world, int rank) {
-  const int T2 = (n64 + 127) / 128, S = 4, TS = (T2 + S - 1) / S;
-  std::vector<std::vector<L1Item>> xl(8);
-  int gi = 0;
-  for (int f = 0; f < K; ++f)
-    for (int sl = 0; sl < nslice; ++sl)
-      for (int Mr = 0; Mr < TS; ++Mr)
-        for (int Mc = 0; Mc <= Mr; ++Mc) {
-          std::vector<L1Item>& dst = xl[gi % 8];
-          bool any = false;
-          for (int mr = Mr * S; mr < std::min(T2, (Mr + 1) * S); ++mr)
-            for (int mc = Mc * S; mc < std::min(T2, (Mc + 1) * S); ++mc) {
-              if (mc > mr) continue;
-              if ((mr * (mr + 1) / 2 + mc) % world != rank) continue;
-              dst.push_back(L1Item{(int16_t)mr, (int16_t)mc, (int16_t)f, (int16_t)sl});
-              any = true;
-            }
-          if (any) ++gi;
-        }
-  size_t mx = 0;
-  for (auto& v : xl) mx = std::max(mx, v.size());
-  std::vector<L1Item> items(mx * 8, L1Item{0, 0, -1, 0});
-  for (int x = 0; x < 8; ++x)
-    for (size_t j = 0; j < xl[x].size(); ++j) items[8 * j + x] = xl[x][j];
-  return items;
-}
-
 // The same fold Gram for any row-major matrix G [n64][ld] (rows >= L read as zero): the fp64 genotype path of l0_f64.hip.
 // out: [nfold][rtot][n64], lower 64x64 tiles; the right-hand-side row tiles are written as zeros (the caller fills them).
 void rg_launch_fold_gram_rows(hipStream_t st, const double* G, int64_t ld, int L, int n64, int rtot, const double* zero,
@@ -287,19 +256,43 @@ __global__ void k_sum_folds(const double* fold, int64_t msz, int nfold, double* 
 }
 
 // ---- LOCO assembly (write_predictions, Data.cpp:1846-1858): out[c][n] = sum_k pred[k][n] - pred[idx(c)][n] ------------
+// sel != nullptr: pred holds several candidate sets [.][nchr][N]; set number *sel is the one assembled
 __global__ __launch_bounds__(256) void k_loco(const double* pred, int nchr, int64_t N, const int32_t* chrom, int nchrom,
-                                              double* out) {
+                                              double* out, const int32_t* sel) {
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
+  if (sel) pred += (int64_t)sel[0] * nchr * N;
   double tot = 0.0;
   for (int k = 0; k < nchr; ++k) tot += pred[(int64_t)k * N + n];      // fixed order: the reference's rowwise().sum()
   for (int c = 0; c < nchrom; ++c) out[(int64_t)c * N + n] = tot;
   for (int k = 0; k < nchr; ++k) out[(int64_t)(chrom[k] - 1) * N + n] = tot - pred[(int64_t)k * N + n];
 }
 
-int rg_emit_pred(rg_ctx* ctx, hipStream_t st, const double* d_pred, int nchr, int p, double* pred_out) {
+// the candidate set number *sel of cand [.][n] -> out [n]
+__global__ __launch_bounds__(256) void k_pick_set(const double* cand, int64_t n, const int32_t* sel, double* out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) out[e] = cand[(int64_t)sel[0] * n + e];
+}
+
+L1StageAlloc rg_l1_stage_alloc() {
+  L1StageAlloc a;
+  a.host_alloc = [](size_t b) -> void* { void* p = nullptr; if (hipHostMalloc(&p, b, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; };
+  a.host_free = [](void* p) { hipHostFree(p); };
+  a.dev_alloc = [](size_t b) -> void* { void* p = nullptr; if (hipMalloc(&p, b) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; };
+  a.dev_free = [](void* p) { hipFree(p); };
+  return a;
+}
+
+int rg_emit_pred(rg_ctx* ctx, hipStream_t st, const double* d_pred, int nchr, int p, double* pred_out, const int32_t* d_sel,
+                 const int32_t* d_chrom) {
   const int64_t N = ctx->N;
   if (ctx->loco_nchrom <= 0) {
+    if (d_sel) {   // the selected set is known on the device only: gather it, then copy
+      double* d_one = (double*)rg_ws(ctx, 11, sizeof(double) * (size_t)nchr * N);
+      if (!d_one) { ctx->err = "level-1 output: out of device memory"; return RG_ERR_HIP; }
+      hipLaunchKernelGGL(k_pick_set, dim3((unsigned)(((int64_t)nchr * N + 255) / 256)), dim3(256), 0, st, d_pred, (int64_t)nchr * N, d_sel, d_one);
+      d_pred = d_one;
+    }
     RG_HIP(hipMemcpyAsync(pred_out + (int64_t)p * nchr * N, d_pred, sizeof(double) * (size_t)nchr * N, hipMemcpyDeviceToHost, st));
     return RG_OK;
   }
@@ -307,9 +300,13 @@ int rg_emit_pred(rg_ctx* ctx, hipStream_t st, const double* d_pred, int nchr, in
   const int nchrom = ctx->loco_nchrom;
   double* d_out = (double*)rg_ws(ctx, 11, sizeof(double) * (size_t)nchrom * N + sizeof(int32_t) * (size_t)nchr + 64);
   if (!d_out) { ctx->err = "LOCO output: out of device memory"; return RG_ERR_HIP; }
-  int32_t* d_chr = reinterpret_cast<int32_t*>(d_out + (size_t)nchrom * N);
-  RG_HIP(hipMemcpyAsync(d_chr, ctx->loco_chrom.data(), sizeof(int32_t) * nchr, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_loco, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_pred, nchr, N, d_chr, nchrom, d_out);
+  const int32_t* d_chr = d_chrom;
+  if (!d_chr) {
+    int32_t* up = reinterpret_cast<int32_t*>(d_out + (size_t)nchrom * N);
+    RG_HIP(hipMemcpyAsync(up, ctx->loco_chrom.data(), sizeof(int32_t) * nchr, hipMemcpyHostToDevice, st));
+    d_chr = up;
+  }
+  hipLaunchKernelGGL(k_loco, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_pred, nchr, N, d_chr, nchrom, d_out, d_sel);
   RG_HIP(hipMemcpyAsync(pred_out + (int64_t)p * nchrom * N, d_out, sizeof(double) * (size_t)nchrom * N, hipMemcpyDeviceToHost, st));
   return RG_OK;
 }
@@ -333,50 +330,92 @@ __global__ __launch_bounds__(256) void k_tiles_pack(double* fold, int64_t msz, i
   }
 }
 
-// ---- out-of-fold predictions for every tau + the five running sums -----------------------------------
+// ---- one pass over W: out-of-fold predictions for every tau (the five running sums) AND the per-chromosome predictions ---------
+// A sample's final prediction uses the coefficients of the fold model that did not see it (make_predictions, Data.cpp:1242-1258):
+// the same products w * alpha_f the CV sums are made of, summed per chromosome instead of over all columns.  So the pass that
+// forms the CV sums also forms, for EVERY ridge value, the per-chromosome sums (its own chains, restarted at every chromosome:
+// each value is the same sequence of fused multiply-adds the separate prediction pass used to run), and the selected ridge value
+// only picks one of the R1 candidate sets afterwards -- on the device, so that no host wait stands between the two.
 // alpha: [(f*R1 + j)] systems, solution = RHS row 0 (row n64) of each factored system.
-// grid (nchunk), 256 threads, thread = one position.  part: [chunk][R1][3] + ysum [chunk][2]
-#define R1MAX 8
+// grid (nchunk), 256 threads, thread = one position.  part: [chunk][R1MAX][3] + ysum [chunk][2];  cand: [R1][nchr][N] (compact
+// sample order).  W is read 16 columns ahead (two register sets): a wave has the SIMD to itself, so nothing else hides the loads.
+#define R1MAX L1_R1MAX
 #define L1_CT 256
-__global__ __launch_bounds__(256) void k_l1_cv(L1Rows R, const double* alpha /*[K*R1][n64]*/, int R1,
-                                               const int32_t* chunk_seg, const int64_t* chunk_pos,
-                                               const int64_t* chunk_len, double* part) {
+#define L1_U 16
+template <int R1T>
+__global__ __launch_bounds__(256) void k_l1_cvpred(L1Rows R, const double* alpha /*[K*R1][n64]*/, const int32_t* chunk_seg,
+                                                   const int64_t* chunk_pos, const int64_t* chunk_len,
+                                                   const int32_t* chr_col0 /*[nchr+1]*/, int nchr, const int32_t* cidx, int64_t N,
+                                                   double* part, double* cand) {
   __shared__ double sA[L1_CT][R1MAX];
-  __shared__ double sred[4][R1MAX * 3 + 2];
+  __shared__ double sred[4][L1_NPART];
   const int ch = blockIdx.x;
   const int f = chunk_seg[ch];
   const int64_t p0 = chunk_pos[ch], plen = chunk_len[ch];
-  double tot[R1MAX * 3 + 2];
+  const int64_t stride = (int64_t)R.P * R.Np;
+  double tot[L1_NPART];
 #pragma unroll
-  for (int t = 0; t < R1MAX * 3 + 2; ++t) tot[t] = 0.0;
+  for (int t = 0; t < L1_NPART; ++t) tot[t] = 0.0;
   for (int64_t sub = 0; sub < plen; sub += 256) {
-    const int64_t pos = p0 + sub + threadIdx.x;
     const bool live = sub + threadIdx.x < plen;
-    double acc[R1MAX];
+    const int64_t pos = live ? p0 + sub + threadIdx.x : p0;      // idle threads read a valid position and store nothing
+    const int32_t n = live ? cidx[pos] : -1;
+    double acc[R1T], pc[R1T];
 #pragma unroll
-    for (int j = 0; j < R1MAX; ++j) acc[j] = 0.0;
+    for (int j = 0; j < R1T; ++j) { acc[j] = 0.0; pc[j] = 0.0; }
+    int cc = 0, cend = chr_col0[1];                              // current chromosome, first column past it
+    auto flush = [&]() {                                         // chromosome cc is complete
+#pragma unroll
+      for (int j = 0; j < R1T; ++j) {
+        if (n >= 0) cand[((int64_t)j * nchr + cc) * N + n] = pc[j];
+        pc[j] = 0.0;
+      }
+    };
     for (int c0 = 0; c0 < R.L; c0 += L1_CT) {
       __syncthreads();
-      for (int j = 0; j < R1MAX; ++j) {
+#pragma unroll
+      for (int j = 0; j < R1T; ++j) {
         const int col = c0 + threadIdx.x;
-        sA[threadIdx.x][j] = (j < R1 && col < R.L)
-            ? alpha[((int64_t)f * R1 + j) * R.n64 + col] : 0.0;
+        sA[threadIdx.x][j] = col < R.L ? alpha[((int64_t)f * R1T + j) * R.n64 + col] : 0.0;
       }
       __syncthreads();
-      if (live) {
-        const int cn = min(L1_CT, R.L - c0);
-        const double* w = R.W + ((int64_t)c0 * R.P + R.p) * R.Np + pos;
-        for (int c = 0; c < cn; ++c) {
-          const double x = w[(int64_t)c * R.P * R.Np];
+      const int cn = min(L1_CT, R.L - c0);
+      const double* w = R.W + ((int64_t)c0 * R.P + R.p) * R.Np + pos;
+      auto use1 = [&](double x, int c) {
+        while (c0 + c == cend && cc + 1 < nchr) { flush(); ++cc; cend = chr_col0[cc + 1]; }
 #pragma unroll
-          for (int j = 0; j < R1MAX; ++j) acc[j] = fma(x, sA[c][j], acc[j]);
+        for (int j = 0; j < R1T; ++j) {
+          acc[j] = fma(x, sA[c][j], acc[j]);
+          pc[j] = fma(x, sA[c][j], pc[j]);
+        }
+      };
+      auto ld = [&](double (&x)[L1_U], int c) {
+#pragma unroll
+        for (int u = 0; u < L1_U; ++u) x[u] = w[(int64_t)(c + u) * stride];
+      };
+      auto use = [&](const double (&x)[L1_U], int c) {
+#pragma unroll
+        for (int u = 0; u < L1_U; ++u) use1(x[u], c + u);
+      };
+      const int cfull = cn / L1_U * L1_U;
+      double xa[L1_U], xb[L1_U];
+      if (cfull > 0) ld(xa, 0);
+      for (int c = 0; c < cfull; c += 2 * L1_U) {
+        const bool more = c + L1_U < cfull;
+        if (more) ld(xb, c + L1_U);
+        use(xa, c);
+        if (more) {
+          if (c + 2 * L1_U < cfull) ld(xa, c + 2 * L1_U);
+          use(xb, c + L1_U);
         }
       }
+      for (int c = cfull; c < cn; ++c) use1(w[(int64_t)c * stride], c);
     }
+    while (cc < nchr) { flush(); ++cc; }                          // the last chromosome (and empty ones after it: zeros)
     if (live) {
       const double y = R.y[pos];
 #pragma unroll
-      for (int j = 0; j < R1MAX; ++j) {
+      for (int j = 0; j < R1T; ++j) {
         tot[3 * j] += acc[j];
         tot[3 * j + 1] = fma(acc[j], acc[j], tot[3 * j + 1]);
         tot[3 * j + 2] = fma(acc[j], y, tot[3 * j + 2]);
@@ -386,44 +425,55 @@ __global__ __launch_bounds__(256) void k_l1_cv(L1Rows R, const double* alpha /*[
     }
   }
 #pragma unroll
-  for (int t = 0; t < R1MAX * 3 + 2; ++t) {
+  for (int t = 0; t < L1_NPART; ++t) {
     double x = tot[t];
     for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6][t] = x;
   }
   __syncthreads();
-  if (threadIdx.x < R1MAX * 3 + 2)
-    part[(int64_t)ch * (R1MAX * 3 + 2) + threadIdx.x] =
+  if (threadIdx.x < L1_NPART)
+    part[(int64_t)ch * L1_NPART + threadIdx.x] =
         (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
 }
 
-// ---- final per-chromosome predictions with the selected tau ------------------------------------------------
-// pred: [nchr][N] (compact sample order); thread = one position
-__global__ __launch_bounds__(256) void k_l1_pred(L1Rows R, const double* alpha /*[K*R1][n64]*/, int R1,
-                                                 int best, const int32_t* chunk_seg,
-                                                 const int64_t* chunk_pos, const int64_t* chunk_len,
-                                                 const int32_t* chr_col0 /*[nchr+1]*/, int nchr,
-                                                 const int32_t* cidx, int64_t N, double* pred) {
-  extern __shared__ double sAl[];  // [L]
-  const int ch = blockIdx.x;
-  const int f = chunk_seg[ch];
-  const int64_t p0 = chunk_pos[ch], plen = chunk_len[ch];
-  const double* al = alpha + ((int64_t)f * R1 + best) * R.n64;
-  for (int c = threadIdx.x; c < R.L; c += 256) sAl[c] = al[c];
-  __syncthreads();
-  for (int64_t sub = 0; sub < plen; sub += 256) {
-    const int64_t pos = p0 + sub + threadIdx.x;
-    if (sub + threadIdx.x >= plen) continue;
-    const int32_t n = cidx[pos];
-    if (n < 0) continue;
-    for (int c = 0; c < nchr; ++c) {
-      double acc = 0.0;
-      const double* w = R.W + ((int64_t)chr_col0[c] * R.P + R.p) * R.Np + pos;
-      const int nn = chr_col0[c + 1] - chr_col0[c];
-      for (int t = 0; t < nn; ++t) acc = fma(w[(int64_t)t * R.P * R.Np], sAl[chr_col0[c] + t], acc);
-      pred[(int64_t)c * N + n] = acc;
-    }
+// ---- cumsum_values (Step1_Models.cpp:854-858) and the selected ridge value (Data.cpp:1025-1037), on the device -------------------
+// One workgroup.  Thread t < L1_NPART adds component t of the chunk partials in chunk order, starting from 0.0: the sums the host
+// loop of earlier versions formed, bit for bit.  Thread 0 then takes the FIRST minimum of (Sx2 + Sy2 - 2 Sxy) / Neff below 1e10 with
+// a strict `<`: a later ridge value that ties does not replace an earlier one, a NaN never wins, and when nothing is below 1e10
+// (all NaN / inf) index 0 stays -- exactly the host rule it replaces.  2 * Sxy is exact, so the expression rounds the same way
+// whether or not the compiler contracts it.
+__global__ __launch_bounds__(256) void k_l1_select(const double* part, int nch, int R1, const double* neff, const int32_t* info,
+                                                   L1Res* res) {
+  __shared__ double sp[128][L1_NPART];
+  __shared__ double stot[L1_NPART];
+  double t = 0.0;
+  for (int c0 = 0; c0 < nch; c0 += 128) {
+    const int nc = min(128, nch - c0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nc * L1_NPART; e += 256) (&sp[0][0])[e] = part[(int64_t)c0 * L1_NPART + e];
+    __syncthreads();
+    if (threadIdx.x < L1_NPART)
+      for (int c = 0; c < nc; ++c) t += sp[c][threadIdx.x];
   }
+  if (threadIdx.x < L1_NPART) { stot[threadIdx.x] = t; res->tot[threadIdx.x] = t; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sy2 = stot[R1MAX * 3 + 1], ne = neff[0];
+    int best = 0; double minv = 1e10;
+    for (int j = 0; j < R1; ++j) {
+      const double perf = (stot[3 * j + 1] + sy2 - 2 * stot[3 * j + 2]) / ne;
+      if (perf < minv) { best = j; minv = perf; }
+    }
+    res->best = best;
+    res->info = info[1];
+  }
+}
+
+template <int R1T>
+static void l1_launch_cvpred(hipStream_t st, int nch, const L1Rows& R, const double* alpha, const rg_ctx* ctx, const int32_t* col0,
+                             int nchr, double* part, double* cand) {
+  hipLaunchKernelGGL(k_l1_cvpred<R1T>, dim3(nch), dim3(256), 0, st, R, alpha, ctx->d_c256_seg, ctx->d_c256_pos, ctx->d_c256_len,
+                     col0, nchr, ctx->d_cidx, ctx->N, part, cand);
 }
 
 int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_t* cols_per_chr,
@@ -438,16 +488,16 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
   if (!ctx->v_W && ctx->w_nb != ctx->B_total) { ctx->err = "rg_l1_qt: W holds a block range only (rg_set_block_range): level 1 needs the exchanged view"; return RG_ERR_STATE; }
   const double* Wv = ctx->v_W ? ctx->v_W : ctx->d_W;
   const int Pv = ctx->v_W ? ctx->v_np : ctx->P, P = ctx->v_np, p0v = ctx->v_p0;
-  int ltot = 0;
-  std::vector<int32_t> col0(nchr + 1, 0);
-  for (int c = 0; c < nchr; ++c) { col0[c + 1] = col0[c] + cols_per_chr[c]; }
-  ltot = col0[nchr];
+  int64_t ltot = 0;
+  for (int c = 0; c < nchr; ++c) {
+    if (cols_per_chr[c] < 0) { ctx->err = "rg_l1_qt: negative cols_per_chr entry"; return RG_ERR_ARG; }
+    ltot += cols_per_chr[c];
+  }
   if (ltot != L) { ctx->err = "rg_l1_qt: cols_per_chr does not sum to n_blocks*R0"; return RG_ERR_ARG; }
   const int n64 = (int)rg_round_up(L, CT), rtot = n64 + CT, T = n64 / CT;
   const int64_t msz = (int64_t)rtot * n64;
   const int nsys = K * R1;
   const int nch = ctx->n_c256;
-  const int NPART = R1MAX * 3 + 2;
   const int world = ctx->coll_world, rank = ctx->coll_rank;
   // a callback with world == 1 is legal: the shared form then runs with a single rank (its all-reduces are identities)
   const bool multi = ctx->coll_allreduce != nullptr;
@@ -465,9 +515,8 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
   int nslice = (int)std::min<int64_t>(16, std::max<int64_t>(1, (3072 + (int64_t)ntile2 * K - 1) / ((int64_t)ntile2 * K)));
   nslice = (int)std::max<int64_t>(1, std::min<int64_t>(nslice, min_nch / 2));      // >= 8 stages of 16 positions per slice
 
-  double *d_fold = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_wk = nullptr, *d_dinv = nullptr, *d_tau = nullptr,
-         *d_cvp = nullptr, *d_pred = nullptr, *d_alpha = nullptr, *d_pack = nullptr;
-  int32_t* d_col0 = nullptr;
+  double *d_fold = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_wk = nullptr, *d_dinv = nullptr,
+         *d_cvp = nullptr, *d_cand = nullptr, *d_alpha = nullptr, *d_pack = nullptr;
 #define L1_WS(var, slot, type, count)                                                   \
   var = (type*)rg_ws(ctx, slot, sizeof(type) * (size_t)(count));                        \
   if (!var) { ctx->err = "rg_l1_qt: out of device memory"; return RG_ERR_HIP; }
@@ -476,20 +525,28 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
   L1_WS(d_sum, 2, double, msz)
   L1_WS(d_wk, 3, double, msz * std::max(1, nloc))
   L1_WS(d_dinv, 4, double, rg_chol_ws_doubles((size_t)std::max(1, nloc), n64))
-  L1_WS(d_tau, 5, double, R1)
-  L1_WS(d_cvp, 6, double, (size_t)nch * NPART)
-  L1_WS(d_pred, 7, double, (size_t)nchr * ctx->N)
+  L1_WS(d_cvp, 6, double, (size_t)nch * L1_NPART)
+  L1_WS(d_cand, 7, double, (size_t)R1 * nchr * ctx->N)
   L1_WS(d_alpha, 8, double, (size_t)nsys * n64)
-  L1_WS(d_col0, 9, int32_t, nchr + 1)
   if (multi) { L1_WS(d_pack, 10, double, (size_t)ntile * K * CT * CT) }
-  L1Item* d_items = nullptr;
-  const std::vector<L1Item> items = l1_build_items(n64, K, nslice, multi ? world : 1, multi ? rank : 0);
-  L1_WS(d_items, 12, L1Item, items.size())
-  RG_HIP(hipMemcpyAsync(d_items, items.data(), sizeof(L1Item) * items.size(), hipMemcpyHostToDevice, st));
-  RG_HIP(hipStreamSynchronize(st));     // `items` is pageable host memory
 #undef L1_WS
-  RG_HIP(hipMemcpyAsync(d_col0, col0.data(), sizeof(int32_t) * (nchr + 1), hipMemcpyHostToDevice, st));
-  std::vector<double> hpart((size_t)nch * NPART);
+  // shape tables, ridge values and results: the context's page-locked area and its device image (l1_stage.h).  The tables travel
+  // only when the shape changed; the ridge values travel with every call.  No wait: the area outlives the call.
+  L1Stage& S = ctx->l1st;
+  const bool loco = ctx->loco_nchrom > 0;
+  int upload = 0;
+  if (l1_stage_prepare(S, rg_l1_stage_alloc(), n64, K, nslice, multi ? world : 1, multi ? rank : 0, nchr, cols_per_chr,
+                       loco ? (int)ctx->loco_chrom.size() : 0, ctx->loco_chrom.data(), P, R1, &upload)) {
+    ctx->err = "rg_l1_qt: out of page-locked host or device memory for the level-1 tables"; return RG_ERR_HIP;
+  }
+  if (upload) RG_HIP(hipMemcpyAsync(S.dev, S.host, S.table_bytes, hipMemcpyHostToDevice, st));
+  memcpy(S.h<double>(S.off_tau), tau, sizeof(double) * (size_t)P * R1);
+  RG_HIP(hipMemcpyAsync(S.d<double>(S.off_tau), S.h<double>(S.off_tau), sizeof(double) * (size_t)P * R1, hipMemcpyHostToDevice, st));
+  const L1Item* d_items = S.d<L1Item>(S.off_items);
+  const int32_t* d_col0 = S.d<int32_t>(S.off_col0);
+  const int32_t* d_chrom = loco ? S.d<int32_t>(S.off_chrom) : nullptr;
+  L1Res* d_res = S.d<L1Res>(S.off_res);
+  L1Res* h_res = S.h<L1Res>(S.off_res);
   int rc = RG_OK;
   auto lap = [&](double* slot, hipEvent_t e0, hipEvent_t e1) {
     if (!ctx->timing) return;
@@ -498,16 +555,18 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
     hipEventRecord(e0, st);
   };
 
+  int pdone = 0;
   for (int p = 0; p < P && rc == RG_OK; ++p) {
     const int pg = p0v + p, pw = ctx->v_W ? p : pg;
     L1Rows R{Wv, ctx->d_V + (int64_t)(ctx->C + pg) * ctx->Np, ctx->d_zero, ctx->Np, L, Pv, pw, n64};
+    const double* d_tau = S.d<double>(S.off_tau) + (int64_t)p * R1;
     hipEvent_t e0 = ctx->ev0, e1 = ctx->ev1;
     if (ctx->timing) hipEventRecord(e0, st);
     // ---- fold Grams X_f = W_f^T W_f with W_f^T y_f as an extra row ------------------------------------------
     double* gout = nslice > 1 ? d_part : d_fold;
     hipMemsetAsync(gout, 0, sizeof(double) * msz * K * nslice, st);
     L1G128 g{R, rtot, nslice, d_items, gout, msz * K};
-    hipLaunchKernelGGL(k_l1_gram128, dim3((unsigned)items.size()), dim3(256), 0, st, g, ctx->seg);
+    hipLaunchKernelGGL(k_l1_gram128, dim3((unsigned)S.n_items), dim3(256), 0, st, g, ctx->seg);
     if (nslice > 1)
       hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((msz * K + 255) / 256)), dim3(256), 0, st, d_part, msz * K,
                          nslice, msz * K, d_fold);
@@ -521,7 +580,6 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
     hipLaunchKernelGGL(k_sum_folds, dim3((unsigned)((msz + 255) / 256)), dim3(256), 0, st, d_fold, msz, K, d_sum);
     lap(&ctx->tm.ms_l1_gram, e0, e1);
     // ---- the K*R1 systems (sum - X_f + tau_j I) alpha = (sum - X_f^T y_f) -----------------------------------
-    hipMemcpyAsync(d_tau, tau + (int64_t)p * R1, sizeof(double) * R1, hipMemcpyHostToDevice, st);
     hipMemsetAsync(d_alpha, 0, sizeof(double) * (size_t)nsys * n64, st);
     if (nloc > 0) {
       rg_launch_chol_solve_formed_x(st, d_sum, 0, d_fold, msz, K, d_tau, R1, nullptr, L, 1, d_wk, msz, n64, CT, 1,
@@ -534,43 +592,40 @@ int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_
       if (ctx->coll_allreduce(ctx->coll_user, d_alpha, (int64_t)nsys * n64) != 0) { ctx->err = "rg_l1_qt: all-reduce callback failed"; rc = RG_ERR_STATE; break; }
     }
     lap(&ctx->tm.ms_l1_chol, e0, e1);
-    // ---- out-of-fold predictions for every tau, the five sums (every rank: identical, deterministic) -------------
-    hipLaunchKernelGGL(k_l1_cv, dim3(nch), dim3(256), 0, st, R, d_alpha, R1, ctx->d_c256_seg,
-                       ctx->d_c256_pos, ctx->d_c256_len, d_cvp);
-    RG_HIP(hipMemcpyAsync(hpart.data(), d_cvp, sizeof(double) * hpart.size(), hipMemcpyDeviceToHost, st));
-    RG_HIP(hipStreamSynchronize(st));
-    // cumsum_values (Step1_Models.cpp:854-858): fixed-order host reduction of the chunk partials
-    double* cs = cumsum_out + (int64_t)p * 5 * R1;  // [5][R1] row-major per phenotype
-    for (int t = 0; t < 5 * R1; ++t) cs[t] = 0.0;
-    double sy = 0.0, sy2 = 0.0;
-    for (int ch = 0; ch < nch; ++ch) {
-      const double* q = hpart.data() + (size_t)ch * NPART;
-      for (int j = 0; j < R1; ++j) {
-        cs[0 * R1 + j] += q[3 * j];
-        cs[2 * R1 + j] += q[3 * j + 1];
-        cs[4 * R1 + j] += q[3 * j + 2];
-      }
-      sy += q[R1MAX * 3];
-      sy2 += q[R1MAX * 3 + 1];
+    // ---- one pass over W: the CV sums of every tau and the candidate predictions (every rank: identical, deterministic); the sums
+    //      are reduced and the ridge value selected on the device; the selected candidate set goes out.  Every compact sample owns one
+    //      position of one chunk (rg_set_problem), so every entry of d_cand is written.
+    switch (R1) {
+      case 1: l1_launch_cvpred<1>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 2: l1_launch_cvpred<2>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 3: l1_launch_cvpred<3>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 4: l1_launch_cvpred<4>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 5: l1_launch_cvpred<5>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 6: l1_launch_cvpred<6>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      case 7: l1_launch_cvpred<7>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
+      default: l1_launch_cvpred<8>(st, nch, R, d_alpha, ctx, d_col0, nchr, d_cvp, d_cand); break;
     }
-    for (int j = 0; j < R1; ++j) { cs[1 * R1 + j] = sy; cs[3 * R1 + j] = sy2; }
-    // Data.cpp:1025-1037: first minimum of (Sx2 + Sy2 - 2 Sxy) / Neff
-    int best = 0; double minv = 1e10;
-    for (int j = 0; j < R1; ++j) {
-      const double perf = (cs[2 * R1 + j] + cs[3 * R1 + j] - 2 * cs[4 * R1 + j]) / ctx->neff[pg];
-      if (perf < minv) { best = j; minv = perf; }
-    }
-    best_out[p] = best;
-    hipMemsetAsync(d_pred, 0, sizeof(double) * (size_t)nchr * ctx->N, st);
-    hipLaunchKernelGGL(k_l1_pred, dim3(nch), dim3(256), sizeof(double) * L, st, R, d_alpha, R1, best,
-                       ctx->d_c256_seg, ctx->d_c256_pos, ctx->d_c256_len, d_col0, nchr,
-                       ctx->d_cidx, ctx->N, d_pred);
-    if ((rc = rg_emit_pred(ctx, st, d_pred, nchr, p, pred_out))) break;
-    RG_HIP(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(k_l1_select, dim3(1), dim3(256), 0, st, d_cvp, nch, R1, ctx->d_neff + pg, ctx->d_info, d_res + p);
+    if ((rc = rg_emit_pred(ctx, st, d_cand, nchr, p, pred_out, &d_res[p].best, d_chrom))) break;
+    RG_HIP(hipMemcpyAsync(h_res + p, d_res + p, sizeof(L1Res), hipMemcpyDeviceToHost, st));
+    ++pdone;
     if (ctx->timing) { hipEventRecord(e1, st); hipEventSynchronize(e1); float ms; hipEventElapsedTime(&ms, e0, e1); ctx->tm.ms_l1_pred += ms; }
-    int32_t info[2] = {0, 0};
-    RG_HIP(hipMemcpy(info, ctx->d_info, sizeof(info), hipMemcpyDeviceToHost));
-    if (info[1]) { ctx->err = "level 1 ridge system is not positive definite"; rc = RG_ERR_NOT_SPD; }
+  }
+  // the call's one wait: the CV sums, the selected indices, the flags and the predictions have all landed
+  RG_HIP(hipStreamSynchronize(st));
+  for (int p = 0; p < pdone; ++p) {
+    const L1Res& r = h_res[p];
+    double* cs = cumsum_out + (int64_t)p * 5 * R1;  // [5][R1] row-major per phenotype
+    for (int j = 0; j < R1; ++j) {
+      cs[0 * R1 + j] = r.tot[3 * j];
+      cs[1 * R1 + j] = r.tot[R1MAX * 3];
+      cs[2 * R1 + j] = r.tot[3 * j + 1];
+      cs[3 * R1 + j] = r.tot[R1MAX * 3 + 1];
+      cs[4 * R1 + j] = r.tot[3 * j + 2];
+    }
+    best_out[p] = r.best;
+    if (r.info && rc == RG_OK) { ctx->err = "level 1 ridge system is not positive definite"; rc = RG_ERR_NOT_SPD; }
   }
   return rc;
 }
+

@@ -85,6 +85,7 @@ void rg_destroy(rg_ctx* c) {
   if (c->ev_tw_join) hipEventDestroy(c->ev_tw_join);
   hipStreamSynchronize(c->stream);
   free_all(c);
+  l1_stage_release(c->l1st, rg_l1_stage_alloc());
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   if (c->ev_fork) {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/rg_step1.h"
+#include "l1_stage.h"
 
 #define RG_MAX_SEG 32      // max CV folds handled by the fold-aligned layout
 #define RG_TILE_G 128      // i8 Gram output tile
@@ -179,6 +180,8 @@ struct rg_ctx {
   // level-1 workspaces, kept across calls (hipMalloc/hipFree per call costs milliseconds)
   void* ws_ptr[16] = {};
   size_t ws_bytes[16] = {};
+  // K-fold level 1: shape tables, ridge values and results in one page-locked area with a device image (l1_stage.h); released by rg_destroy
+  L1Stage l1st;
 
   // fp64 genotype input (l0_f64.hip): grows-only device buffers of the dosage path
   void* f64_ptr[10] = {};
@@ -344,7 +347,12 @@ int rg_l0_blocks_f64_impl(rg_ctx* ctx, int nblk, const int32_t* block_ids, const
 // l1.hip
 // copies the per-chromosome predictions of one phenotype (device, [nchr][N]) to the caller: as they are, or assembled
 // into LOCO rows [nchrom][N] first (rg_set_loco_output).  Returns an RG_* code.
-int rg_emit_pred(rg_ctx* ctx, hipStream_t st, const double* d_pred, int nchr, int p, double* pred_out);
+// d_sel != nullptr: d_pred holds several candidate sets [.][nchr][N] and the one to emit is number *d_sel, read on the device.
+// d_chrom != nullptr: the chromosome ids of rg_set_loco_output are already on the device (else they are uploaded here).
+int rg_emit_pred(rg_ctx* ctx, hipStream_t st, const double* d_pred, int nchr, int p, double* pred_out, const int32_t* d_sel = nullptr,
+                 const int32_t* d_chrom = nullptr);
+// the allocators of the context's level-1 staging area (page-locked host memory, device memory)
+L1StageAlloc rg_l1_stage_alloc();
 struct L1Args;
 int rg_l1_qt_impl(rg_ctx* ctx, int R1, const double* tau, int nchr, const int32_t* cols_per_chr,
                   double* cumsum_out, int32_t* best_out, double* pred_out);

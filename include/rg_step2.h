@@ -211,6 +211,26 @@ int rg_s2_bt_correct(rg_s2_ctx* ctx, int32_t kind, int32_t npair, const int32_t*
 typedef struct rg_s2_mcc_out { double* sums; /* [nv][P][7], HOST pointer */ } rg_s2_mcc_out;
 int rg_s2_qt_moments(rg_s2_ctx* ctx, int32_t nv, const int32_t* variant, const rg_s2_mcc_out* out);
 
+/* ---- counts of a block restricted to a sample group (chromosome X outside the pseudo-autosomal regions; csrc/step2_group.hip) --------------------
+ * The reference counts a male's call at half its value in the minor-allele count of a non-PAR variant of chromosome X (parseSnpfromBed and its
+ * like, Geno.cpp:2445-2471; compute_mac, :3077-3108: MAC = min(mac, 2 ns - nmales - mac); per trait update_trait_counts, :2948-2959) and changes
+ * nothing else under its default dosage compensation.  With the group = the males, a caller gets what that rule needs from:
+ *   rg_s2_set_group            member [n] host bytes (0 / 1; NULL clears the group and frees what it held).  The membership, and membership AND mask_p
+ *                              for each of the P trait masks, are packed once into bit planes laid out like a 2-bit row.  mask [P][n] host bytes, or
+ *                              NULL for the masks of rg_s2_set_null (the planes are packed again when that call brings new masks); a caller of
+ *                              rg_s2_bt_set_null hands its masks over here.
+ *   rg_s2_group_counts_packed  2-bit rows as rg_s2_qt_block_packed takes them (host or device, ld >= ceil(n / 4) bytes, any padding; flip as there)
+ *                              -> counts [bs][1 + P][3] = calls equal to 1, equal to 2, observed among the group (plane 0) and among the group's
+ *                              samples observed for trait p (plane 1 + p).  ADDITIVE under every coding: it reads the caller's rows, not the staged
+ *                              and relabelled ones.
+ *   rg_s2_group_sums_int       uint16 rows as rg_s2_qt_block_int takes them (host or device, ld >= n elements, 0xFFFF = missing)
+ *                              -> sums [bs][1 + P][2] int64 = exact sum of the observed values (units of 1 / scale), observed count.
+ * Both take rows of their own and leave the block a score entry staged alone (rg_s2_bt_correct, rg_s2_qt_moments, rg_s2_packed_counts still see it).
+ * A context with no group set launches and allocates nothing of this.  Host pointers for member, mask, counts, sums. */
+int rg_s2_set_group(rg_s2_ctx* ctx, const uint8_t* member, const uint8_t* mask);
+int rg_s2_group_counts_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, int32_t* counts);
+int rg_s2_group_sums_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int64_t* sums);
+
 /* Device time of the kernels of the last rg_s2_qt_block / rg_s2_qt_block_packed / rg_s2_qt_moments call (hipEvents on the library's stream), in ms. */
 double rg_s2_last_kernel_ms(const rg_s2_ctx* ctx);
 

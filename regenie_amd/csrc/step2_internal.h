@@ -93,6 +93,9 @@ struct rg_s2_ctx {
   size_t tcnt_cap = 0;
   bool tcnt_valid = false;
   const uint8_t* contract_mask = nullptr;      // set by rg_s2_bt_score_packed around its rg_s2_contract_packed call: the traits' device masks
+  // ---- rg_s2_set_group (step2_group.hip): the bit planes of a sample group; null until a group is set ----
+  struct GroupState* grp = nullptr;
+  int mask_gen = 0;             // counts the rg_s2_set_null calls that brought new masks (the group's planes are packed against them)
 };
 
 
@@ -134,3 +137,4 @@ static inline int rg_s2_fetch_trait_counts(rg_s2_ctx* ctx, int bs, std::vector<i
 }
 void rg_s2_bt_free(rg_s2_ctx* ctx);   // step2_bt.hip
 void rg_s2_mcc_free(rg_s2_ctx* ctx);  // step2_mcc.hip
+void rg_s2_group_free(rg_s2_ctx* ctx);  // step2_group.hip

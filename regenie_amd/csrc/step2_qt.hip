@@ -1340,6 +1340,7 @@ void rg_s2_destroy(rg_s2_ctx* ctx) {
     if (ctx->d_tcnt) (void)hipFree(ctx->d_tcnt);
     rg_s2_bt_free(ctx);
     rg_s2_mcc_free(ctx);
+    rg_s2_group_free(ctx);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
     if (ctx->e1) (void)hipEventDestroy(ctx->e1);
     (void)hipStreamDestroy(ctx->st);
@@ -1367,6 +1368,7 @@ int rg_s2_set_null(rg_s2_ctx* ctx, const double* X, const double* yres, const ui
     ctx->hM.assign(mask, mask + nm);
     ctx->static_ready = false;
     ctx->lists_ready = false;
+    ++ctx->mask_gen;
     ctx->complete = true;
     for (size_t i = 0; i < nm; ++i)
       if (!mask[i]) { ctx->complete = false; break; }

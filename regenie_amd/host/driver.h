@@ -130,6 +130,13 @@ struct Params {
   int test_type = 0;
   bool saw_test = false;
   double min_homs = 0.0;
+  // --step 2 --par-region hg38|hg19|hg18|b38|b37|b36|<end_par1>,<start_par2> (Regenie.cpp:253, check_build_code :1643-1660): the bounds of the
+  // pseudo-autosomal regions of chromosome X.  A variant of chromosome X with par1_max < pos < par2_min is non-PAR (in_non_par, Geno.cpp:2802-2814):
+  // there a male's call counts half in the minor-allele count.  The reference defaults to hg38 without a word; here chromosome X with males is
+  // tested only when the build is named.
+  bool par_set = false;
+  std::string build_code;
+  int64_t par1_max = 0, par2_min = 0;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards
@@ -247,7 +254,8 @@ struct Run {
   int64_t n_file = 0, bpr = 0;
   rg_pgen* pgen = nullptr;               // --pgen: open reader (bed rows come from rg_pgen_read_bed_rows)
   bool dosage_mode = false;              // --pgen with dosage tracks / --bgen: rows of doubles, level 0 from rg_l0_blocks_f64
-  bool has_male = false;                 // a sample with sex code 1 in the .fam / .psam (Step 2 on chromosome X needs it)
+  bool has_male = false;                 // a sample with sex code 1 in the .fam / .psam / .sample (Step 2 on chromosome X needs it)
+  std::vector<uint8_t> sex;              // per sample of the file: the sex code (0: unknown / NA, 1: male, 2: female; params->sex)
   rg_bgen* bgenh = nullptr;              // --bgen: open reader
   // --condition-list: the conditioning variants in ascending id order (filters->condition_snp_names is a std::map, Geno.cpp:4151-4179) with their
   // index in the main genotype file (-1: not met among the variants the chromosome / range filter leaves)

@@ -370,6 +370,9 @@ Params parse_args(int argc, char** argv) {
       p.min_homs = std::strtod(v.c_str(), &end);
       if (v.empty() || *end != '\0') usage_error("Argument \u2018" + v + "\u2019 failed to parse");      // the option parser's own message
     }
+    else if (a == "--par-region") { p.build_code = need(i); p.par_set = true; }            // "build code to identify PAR region boundaries on chrX" (Regenie.cpp:253)
+    else if (a == "--skip-dosage-comp") usage_error("--skip-dosage-comp (males' genotypes halved in the tested vector and in A1FREQ outside the PAR regions of chromosome X) is not built.");
+    else if (a == "--sex-specific") { need(i); usage_error("--sex-specific (male-only / female-only analyses) is not built."); }
     else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
     else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
     else if (a == "--forcein-vars") p.forcein_vars = true;
@@ -452,6 +455,19 @@ Params parse_args(int argc, char** argv) {
     if (p.gpus > 1) usage_error("--compute-corr on more than one GPU (--gpus) is not built.");
     if (p.forcein_vars && p.extract.size() > 1) usage_error("cannot have multiple extract files");      // Geno.cpp:1352
     p.forcein_vars = p.forcein_vars && !p.extract.empty();
+  }
+  if (p.par_set) {               // check_build_code (Regenie.cpp:1643-1660), which the reference runs in test mode
+    if (p.step != 2) usage_error("can only use --par-region in step 2 (association testing).");
+    const std::string& b = p.build_code;
+    if (b == "b36" || b == "hg18") { p.par1_max = 2709520; p.par2_min = 154584238; }
+    else if (b == "b37" || b == "hg19") { p.par1_max = 2699520; p.par2_min = 154931044; }
+    else if (b == "b38" || b == "hg38") { p.par1_max = 2781479; p.par2_min = 155701383; }
+    else {                       // <end_par1>,<start_par2>: the first and the last position of the non-PAR region
+      int lo = 0, hi = 0;
+      if (sscanf(b.c_str(), "%d,%d", &lo, &hi) != 2 || lo < 1 || hi < 1 || hi < lo)
+        usage_error("invalid build code given (valid ones are 'b36|b37|b38|hg18|hg19|hg38' or [start,end] position of the non-par region)");
+      p.par1_max = (int64_t)lo - 1; p.par2_min = (int64_t)hi + 1;
+    }
   }
   if (p.saw_test && p.step != 2) usage_error("can only use --test in step 2 (association testing).");      // Regenie.cpp:906-907
   if (p.test_type > 0 && p.compute_corr) usage_error("--test dominant / recessive with --compute-corr (the LD matrix of recoded genotypes) is not built.");

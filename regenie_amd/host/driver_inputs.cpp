@@ -114,6 +114,8 @@ void read_bgen_meta(Run& r) {
       else {
         r.fam_ids.push_back(t[0] + "_" + t[1]);
         if (t.size() >= 4 && t[3] != "0" && t[3] != "NA" && t[3] != "1" && t[3] != "2") throw std::runtime_error("unrecognized sex code in file : '" + t[3] + "'");
+        r.sex.push_back(t.size() >= 4 && t[3] == "1" ? 1 : t.size() >= 4 && t[3] == "2" ? 2 : 0);      // the fourth column (read_bgen_sample, Geno.cpp:438-443)
+        if (r.sex.back() == 1) r.has_male = true;
       }
       ++nline;
     }
@@ -169,6 +171,7 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
         const bool one = t[4].e - t[4].b == 1;
         if (!one || (*t[4].b != '0' && *t[4].b != '1' && *t[4].b != '2')) throw std::runtime_error("unrecognized sex code in file : '" + std::string(t[4].b, t[4].e) + "'");
         if (*t[4].b == '1') r.has_male = true;
+        r.sex.push_back((uint8_t)(*t[4].b - '0'));
         r.fam_ids.push_back(std::move(id));
       }
       r.n_file = (int64_t)r.fam_ids.size();
@@ -202,7 +205,8 @@ void read_bim_fam(Run& r) {  // bed: Geno.cpp:518-610, :643-690, :1128-1220; pge
         const std::string& sx = t[sex_col];
         if (sx != "0" && sx != "NA" && sx != "1" && sx != "2") throw std::runtime_error("unrecognized sex code in file : '" + sx + "'");
         if (sx == "1") r.has_male = true;
-      }
+        r.sex.push_back(sx == "1" ? 1 : sx == "2" ? 2 : 0);
+      } else r.sex.push_back(0);
       r.fam_ids.push_back(id);
     }
     r.n_file = (int64_t)r.fam_ids.size();

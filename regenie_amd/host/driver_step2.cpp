@@ -38,7 +38,14 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p)
   // --threads as given, or every hardware thread but two, shared by the parts of a multi-GPU run
   nt_prep = env.prep_threads ? env.prep_threads : std::max(1, std::min(p.threads > 0 ? p.threads : usable_cpus(), 256) / part.nparts);
   ld16 = (n + 7) / 8 * 8;
-  fast_bgen = in == In::Dosage && r.bgenh && (!env.dense || glm) && !(correct && !spa && !p.firth_approx) && !env.bgen_rows;
+  // chromosome X with males under --par-region: the analysed samples' sex (without --par-region run_step2 refuses)
+  if (chr_snps.count(p.nchrom) && r.has_male && p.par_set) {
+    sex_aware = true;
+    male.assign(n, 0);
+    for (int64_t k = 0; k < n; ++k) male[k] = (r.sex.size() == (size_t)r.n_file && r.sex[file_idx[k]] == 1) ? 1 : 0;
+  }
+  // (the device decoder's rows hold the CODED probabilities under --test dominant | recessive: the males' additive sums then come from the general rows)
+  fast_bgen = in == In::Dosage && r.bgenh && (!env.dense || glm) && !(correct && !spa && !p.firth_approx) && !env.bgen_rows && !(sex_aware && coding);
 }
 
 // .bed rows of a block: runs of consecutive variants are cut into pieces read by several threads (the page-cache copy of one pread is a
@@ -275,7 +282,33 @@ struct BlockCounts {
   std::vector<int64_t> ns1, ns_t;
   std::vector<uint8_t> variant_ignored;
   std::vector<double> sum_pos;      // --test dominant | recessive: the recoded vector's sum over the observed samples (the counts above stay additive)
-  explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0), sum_pos(bs, 0.0) {}
+  // non-PAR variants of chromosome X (S2Common::sex_aware): the MALES' allele total and observed count, [bs][1 + P] = overall, then among the samples
+  // observed for trait q (update_trait_counts' mac / nmales, Geno.cpp:2948-2959) -- filled by the input route (host loops) or fetch_group (device)
+  std::vector<uint8_t> nonpar, het_male;
+  bool any_nonpar = false;
+  int P1 = 1;
+  std::vector<double> msum;
+  std::vector<int64_t> mobs;
+  explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0), sum_pos(bs, 0.0), nonpar(bs, 0), het_male(bs, 0) {}
+  void mark_non_par(const S2Common& cm, const std::vector<int64_t>& snps, int64_t j0) {
+    if (!cm.sex_aware) return;
+    P1 = 1 + cm.P;
+    for (size_t j = 0; j < nonpar.size(); ++j) if ((nonpar[j] = cm.non_par(snps[j0 + (int64_t)j]) ? 1 : 0)) any_nonpar = true;
+    if (any_nonpar) { msum.assign(nonpar.size() * P1, 0.0); mobs.assign(nonpar.size() * P1, 0); }
+  }
+  // a male's observed call v of a non-PAR variant j, sample k (host routes)
+  void add_male(const S2Common& cm, int j, int64_t k, double v) {
+    double* ms = &msum[(size_t)j * P1]; int64_t* mo = &mobs[(size_t)j * P1];
+    ms[0] += v; mo[0] += 1;
+    for (int q = 0; q < cm.P; ++q) if (cm.Mc[(size_t)q * cm.n + k]) { ms[1 + q] += v; mo[1 + q] += 1; }
+  }
+  // compute_mac (Geno.cpp:3077-3108) for the variant (all samples) and for a trait's samples: allele total tq over nsq observed samples
+  bool low_mac(int j, double min_mac) const {
+    return nonpar[j] ? below_min_mac_x(total[j], (double)ns1[j], msum[(size_t)j * P1], (double)mobs[(size_t)j * P1], min_mac) : below_min_mac(total[j], (double)ns1[j], min_mac);
+  }
+  bool low_mac_t(int j, int q, double tq, double nsq, double min_mac) const {
+    return nonpar[j] ? below_min_mac_x(tq, nsq, msum[(size_t)j * P1 + 1 + q], (double)mobs[(size_t)j * P1 + 1 + q], min_mac) : below_min_mac(tq, nsq, min_mac);
+  }
 };
 
 // One block through the tests: an input route leaves the counts and the genotype source, the scorer the statistics, correct() the
@@ -340,6 +373,15 @@ struct S2Block {
     if (cm.coding) bc.sum_pos.assign(pb.sum_pos, pb.sum_pos + bs);
     if (cm.per_trait) { bc.af_t.assign(pb.af_t, pb.af_t + bs * P); bc.ns_t.assign(pb.ns_t, pb.ns_t + bs * P); bc.info_t.assign(pb.info_t, pb.info_t + bs * P); }
     integral = true; g16p = pb.g16; g16ld = pb.ld; g16_on_device = pb.on_device;
+    if (!bc.any_nonpar) return;
+    // the males' sums of the prepared rows (device-decoded rows never leave the GPU): exact integers in units of 1 / scale
+    std::vector<int64_t> gs((size_t)bs * bc.P1 * 2);
+    check(rg_s2_group_sums_int(s2, g16p, g16ld, bs, g16_on_device, gs.data()));
+    for (int j = 0; j < bs; ++j) {
+      if (!bc.nonpar[j]) continue;
+      for (int q = 0; q < bc.P1; ++q) { bc.msum[(size_t)j * bc.P1 + q] = (double)gs[((size_t)j * bc.P1 + q) * 2] / cm.dscale; bc.mobs[(size_t)j * bc.P1 + q] = gs[((size_t)j * bc.P1 + q) * 2 + 1]; }
+      bc.variant_ignored[j] = bc.low_mac(j, cm.p.min_mac) ? 1 : 0;      // (the read-ahead applied the autosomal rule, which never drops what this one keeps)
+    }
   }
 
   // route 2, general dosage rows: the analysed samples' doubles, allele totals, the info-score numerator and the per-trait corrections on the
@@ -368,10 +410,11 @@ struct S2Block {
         }
         const double e = iv ? iv[i] : v * v;
         tot += v; inf += e; ++ns;
+        if (bc.nonpar[j] && cm.male[k]) bc.add_male(cm, j, k, v);
         if (cm.per_trait && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, v, e, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], &bc.info_t[(size_t)j * P]);
       }
       bc.total[j] = tot; bc.ns1[j] = ns; bc.info_num[j] = inf; bc.sum_pos[j] = pos;
-      if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
+      if (bc.low_mac(j, cm.p.min_mac)) bc.variant_ignored[j] = 1;
     });
     // 8-bit .bgen probabilities and .pgen dosages are integers in units of 1 / 255 and 1 / 16384: as uint16 rows they take the
     // integer route of the library (digit planes on the i8 matrix cores, 2 B per genotype over PCIe); anything else, or
@@ -421,11 +464,12 @@ struct S2Block {
         if (hc != -3.0) {
           if (cm.coding) { g[k] = recode_hard_call(hc, cm.coding); pos += g[k]; }
           tot += hc; ++ns;
+          if (bc.nonpar[j] && cm.male[k]) { bc.add_male(cm, j, k, hc); if (hc == 1.0) bc.het_male[j] = 1; }
           if (cm.any_missing && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, hc, 0.0, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], nullptr);
         }
       }
       bc.total[j] = tot; bc.ns1[j] = ns; bc.sum_pos[j] = pos;
-      if (below_min_mac(tot, (double)ns, cm.p.min_mac)) bc.variant_ignored[j] = 1;
+      if (bc.low_mac(j, cm.p.min_mac)) bc.variant_ignored[j] = 1;
     });
   }
 
@@ -436,6 +480,22 @@ struct S2Block {
     for (int j = 0; j < bs; ++j) {
       if (cm.coding == 2 && bc.sum_pos[j] < cm.p.min_homs) bc.variant_ignored[j] = 1;
       if (bc.ns1[j] > 0 && bc.sum_pos[j] / (double)bc.ns1[j] < NUMTOL) bc.variant_ignored[j] = 1;
+    }
+  }
+
+  // hard calls that stayed packed, a block with a non-PAR variant of chromosome X: the males' calls equal to 1, equal to 2 and observed, overall
+  // and among each trait's samples, from the library (rg_s2_group_counts_packed reads the rows the score entry was given; additive under every coding)
+  void fetch_group(BlockCounts& bc) {
+    if (!bc.any_nonpar) return;
+    std::vector<int32_t> gc((size_t)bs * bc.P1 * 3);
+    check(rg_s2_group_counts_packed(s2, rows, ld, bs, 0, cm.flip, gc.data()));
+    for (int j = 0; j < bs; ++j) {
+      if (!bc.nonpar[j]) continue;
+      for (int q = 0; q < bc.P1; ++q) {
+        const int32_t* c = &gc[((size_t)j * bc.P1 + q) * 3];
+        bc.msum[(size_t)j * bc.P1 + q] = (double)c[0] + 2.0 * c[1]; bc.mobs[(size_t)j * bc.P1 + q] = c[2];
+      }
+      if (gc[(size_t)j * bc.P1 * 3] > 0) bc.het_male[j] = 1;
     }
   }
 
@@ -466,6 +526,7 @@ struct S2Block {
       o.total_p = totp_v.data(); o.n_obs_p = nobsp_v.data();
     }
     check(rg_s2_qt_block_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &o));
+    fetch_group(bc);
     std::vector<int32_t> cnt_v;      // --test dominant | recessive: the mean is the recoded vector's, the additive counts come on their own
     if (cm.coding) { cnt_v.resize((size_t)bs * 4); check(rg_s2_packed_counts(s2, cnt_v.data())); }
     if (cm.any_missing) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); }
@@ -476,7 +537,7 @@ struct S2Block {
         bc.total[j] = n1 + 2.0 * n2; bc.sum_pos[j] = cm.coding == 1 ? n1 + n2 : n2;
       } else
       bc.total[j] = std::nearbyint(mean_v[j] * (double)nobs_v[j]);       // the allele count is an integer: mean = total / n_obs
-      if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
+      if (bc.low_mac(j, cm.p.min_mac)) bc.variant_ignored[j] = 1;
       if (cm.any_missing)                                                  // update_trait_counts (Geno.cpp:2948-2959) as differences from the totals
         for (int q = 0; q < P; ++q) {
           bc.af_t[(size_t)j * P + q] = std::nearbyint(totp_v[(size_t)j * P + q]) - bc.total[j];
@@ -553,6 +614,7 @@ struct S2Block {
     } else {
       bo.counts = bt_counts.data(); bo.total_p = totp.data(); bo.n_obs_p = nobsp.data();
       check(rg_s2_bt_score_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &bo));
+      fetch_group(bc);
       bc.af_t.assign(totp.begin(), totp.end());      // per-trait allele and sample counts (dosages: the route has them, summed as the reference sums)
       bc.ns_t.assign(nobsp.begin(), nobsp.end());
     }
@@ -563,7 +625,7 @@ struct S2Block {
         if (cm.coding) bc.sum_pos[j] = cm.coding == 1 ? n1 + n2 : n2;
       }
       sfac[j] = 1.0;
-      if (below_min_mac(bc.total[j], (double)bc.ns1[j], cm.p.min_mac)) bc.variant_ignored[j] = 1;
+      if (bc.low_mac(j, cm.p.min_mac)) bc.variant_ignored[j] = 1;
     }
   }
 
@@ -590,7 +652,7 @@ struct S2Block {
         else {
           const double tq = bc.total[j] + bc.af_t[(size_t)j * P + q];
           const double nsq = (double)(bc.ns1[j] + bc.ns_t[(size_t)j * P + q]);
-          pf_[t] = sparse_v[j] && below_min_mac(tq, nsq, 50.0);                                       // fit_firth_logistic_snp_fast :1173-1185: carriers only
+          pf_[t] = sparse_v[j] && bc.low_mac_t(j, q, tq, nsq, 50.0);                                       // fit_firth_logistic_snp_fast :1173-1185: carriers only
         }
       }
       std::vector<rg_s2_bt_corr> cr(todo.size());
@@ -665,7 +727,7 @@ struct S2Block {
           if (cm.per_trait) {   // compute_mac / compute_aaf_info per trait
             const double tq = total + bc.af_t[e];
             nsq = ns1 + bc.ns_t[e];
-            if (below_min_mac(tq, (double)nsq, p.min_mac)) { ++c_tests[t]; continue; }
+            if (bc.low_mac_t(j, q, tq, (double)nsq, p.min_mac)) { ++c_tests[t]; continue; }
             af = tq / (2.0 * nsq);
             if (show_info) infq += bc.info_t[e];
           }
@@ -724,9 +786,20 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
   if (cm.coding) blk.check(rg_s2_set_coding(s2, cm.coding));      // (an additive run never calls it)
   // in_non_par (Geno.cpp:2419, :2251): outside the pseudo-autosomal regions of chromosome X the reference halves the males' calls in the
   // MAC (and, with the default dosage compensation off, nothing else) -- with no male in the sample file that is the autosomal rule
-  if (cm.chr_snps.count(p.nchrom) && r.has_male)
+  if (cm.chr_snps.count(p.nchrom) && r.has_male && !p.par_set)
     throw std::runtime_error("--step 2 on chromosome " + std::to_string(p.nchrom) + " (X) with male samples: the sex-aware allele counts of the non-PAR region "
-                             "are not built; test the autosomes (or supply a sample file without sex codes of 1).");
+                             "need the bounds of the pseudo-autosomal regions; give --par-region hg38|hg19|hg18|b37|b36|<end_par1>,<start_par2> "
+                             "(or test the autosomes, or supply a sample file without sex codes of 1).");
+  if (cm.sex_aware) {
+    std::vector<uint8_t> grp(cm.male);
+    blk.check(rg_s2_set_group(s2, grp.data(), cm.Mc.data()));      // (every part of a --gpus N run: its own context)
+    if (part.part == 0) {
+      int64_t nm = 0;
+      for (uint8_t m : cm.male) nm += m;
+      sout << " * chromosome " << p.nchrom << " (X): non-PAR region is (" << p.par1_max << ", " << p.par2_min << ") [--par-region " << p.build_code << "]; "
+           << nm << " analysed males count half in the MAC there\n";
+    }
+  }
   sout << std::left << std::setw(20) << " * block size" << ": [" << p.bsize << "]\n";
   sout << std::left << std::setw(20) << " * # blocks" << ": [" << cm.total_blocks << "]\n";
   sout << " * approximate memory usage : n/a (genotype blocks are tested on the GPU)\n";
@@ -778,12 +851,22 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
       }
       auto t_dev = std::chrono::steady_clock::now();
       BlockCounts bc(bs);
+      bc.mark_non_par(cm, snps, j0);
       if (pb) blk.from_prepared(*pb, bc);
       else if (cm.in == In::Dosage) blk.from_dosage_rows(bc);
       else if (cm.glm || !cm.env.dense) blk.from_packed();
       else blk.from_dense_bed(bc);
       // score, correct, format
       if (cm.glm) blk.score_glm(bc); else blk.score_qt(bc);
+      if (bc.any_nonpar) {     // the reference's warning (Geno.cpp:2453, :2705-2711): a hard call of 1 for a male counts 0.5
+        std::vector<std::string> het;
+        for (int j = 0; j < bs; ++j) if (bc.het_male[j]) het.push_back(r.snp_ids[snps[j0 + j]]);
+        if (!het.empty()) {
+          std::string msg = "WARNING: genotype is 1 for a male on chrX (males should coded as diploid) at variants [";
+          for (size_t h = 0; h < het.size(); ++h) msg += (h ? ";" : "") + het[h];
+          std::cerr << msg + "].\n";
+        }
+      }
       blk.coding_filters(bc);
       if (cm.glm && cm.correct) blk.correct(bc);
       if (cm.mcc) blk.mcc(bc);

@@ -94,11 +94,21 @@ struct S2Common : SampleMap {
   int coding;                                   // --test: 0 additive, 1 dominant, 2 recessive (= RG_S2_ADDITIVE / _DOMINANT / _RECESSIVE)
   const char* test_name;                        // the TEST column: ADD / DOM / REC (Data.cpp:2077-2089)
   int64_t ld16;                                 // leading dimension of the host threads' uint16 dosage rows
+  // chromosome X outside the pseudo-autosomal regions (--par-region): a male's call counts half in the minor-allele count
+  bool sex_aware = false;                       // chromosome X is tested, the sample file has males and --par-region names the bounds
+  std::vector<uint8_t> male;                    // per analysed sample: sex code 1 (params->sex subset to the analysis, Geno.cpp:1330-1332)
+  bool non_par(int64_t snp) const { return sex_aware && r.snp_chrom[snp] == p.nchrom && r.snp_pos[snp] > p.par1_max && r.snp_pos[snp] < p.par2_min; }   // in_non_par (Geno.cpp:2802-2814)
 };
 
 inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 // compute_mac (Geno.cpp:3077-3108), autosomes
 inline bool below_min_mac(double total, double ns, double min_mac) { return std::min(total, 2.0 * ns - total) < min_mac; }
+// the same outside the pseudo-autosomal regions of chromosome X (:3096-3097): mac = sum g (male ? 0.5 : 1) = total - male_total / 2 over the observed
+// samples, of which nmales are male; MAC = min(mac, 2 ns - nmales - mac).  Never above the autosomal value.
+inline bool below_min_mac_x(double total, double ns, double male_total, double nmales, double min_mac) {
+  const double mac = total - 0.5 * male_total;
+  return std::min(mac, 2.0 * ns - nmales - mac) < min_mac;
+}
 // compute_aaf_info (Geno.cpp:3132-3141): IMPUTE info for .bgen (it can be negative for very uncertain dosages), MaCH r2 for .pgen dosages
 inline double info_score(bool bgen, double info_num, double ns, double af) {
   if (af == 0.0 || af == 1.0) return 1.0;

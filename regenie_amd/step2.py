@@ -104,6 +104,63 @@ class Step2QT:
         self._check(self.lib.rg_s2_packed_counts(self.h, counts.ctypes.data))
         return counts
 
+    # ---- counts restricted to a sample group (rg_s2_set_group; chromosome X outside the pseudo-autosomal regions: group = the males) ---------
+    def set_group(self, member, mask=None) -> None:
+        """member [n] 0 / 1 (None clears the group).  mask [P][n]: the trait masks the group is intersected with; None = those of set_null
+        (a bt_set_null caller hands its masks over)."""
+        if member is None:
+            self._check(self.lib.rg_s2_set_group(self.h, None, None))
+            return
+        member = np.ascontiguousarray(np.asarray(member) != 0, dtype=np.uint8)
+        if member.shape != (self.n,):
+            raise ValueError("set_group: member must be [n]")
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape != (self.P, self.n):
+                raise ValueError("set_group: mask must be [P][n]")
+            mp = mask.ctypes.data
+        self._check(self.lib.rg_s2_set_group(self.h, member.ctypes.data, mp))
+
+    def group_counts(self, rows, flip: bool = False) -> np.ndarray:
+        """Hard calls as score_block_packed takes them (numpy, or a CUDA torch uint8 tensor read in place) -> int32 [bs][1 + P][3]: calls equal to 1,
+        equal to 2 and observed among the group (plane 0) and among the group's samples observed for trait p (plane 1 + p).  Additive under every
+        coding; the block a score call staged is left alone."""
+        on_device = 0
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.uint8)
+            bs, ld, ptr = rows.shape[0], rows.shape[1], rows.ctypes.data
+        else:
+            if not (rows.is_cuda and rows.element_size() == 1 and rows.dim() == 2 and rows.stride(1) == 1):
+                raise ValueError("group_counts: device rows must be a 2-d uint8 CUDA tensor with unit byte stride")
+            bs, ld, ptr, on_device = rows.shape[0], rows.stride(0), rows.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(rows.device).synchronize()
+        if rows.shape[1] < (self.n + 3) // 4:
+            raise ValueError("group_counts: rows must hold ceil(n / 4) bytes")
+        counts = np.zeros((bs, 1 + self.P, 3), np.int32)
+        self._check(self.lib.rg_s2_group_counts_packed(self.h, ptr, ld, bs, on_device, 1 if flip else 0, counts.ctypes.data))
+        return counts
+
+    def group_sums_int(self, G) -> np.ndarray:
+        """Integer dosages as score_block_int takes them (uint16, 0xFFFF = missing; numpy, or a CUDA torch tensor of 2-byte elements read in place)
+        -> int64 [bs][1 + P][2]: exact sum of the observed values (units of 1 / scale) and observed count, planes as group_counts."""
+        on_device = 0
+        if isinstance(G, np.ndarray):
+            G = np.ascontiguousarray(G, dtype=np.uint16)
+            bs, ld, ptr = G.shape[0], G.shape[1], G.ctypes.data
+        else:
+            if not (G.is_cuda and G.element_size() == 2 and G.dim() == 2 and G.stride(1) == 1):
+                raise ValueError("group_sums_int: device G must be a 2-d CUDA tensor of 2-byte elements with unit sample stride")
+            bs, ld, ptr, on_device = G.shape[0], G.stride(0), G.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(G.device).synchronize()
+        if G.ndim != 2 or G.shape[1] < self.n:
+            raise ValueError("group_sums_int: G must be [bs][>= n]")
+        sums = np.zeros((bs, 1 + self.P, 2), np.int64)
+        self._check(self.lib.rg_s2_group_sums_int(self.h, ptr, ld, bs, on_device, sums.ctypes.data))
+        return sums
+
     def score_block(self, G, numtol: float = NUMTOL) -> dict:
         """G: numpy [bs][n] float64 (host), or a CUDA torch tensor [bs][n] float64 (read in place).  Missing = NaN or < 0."""
         on_device = 0

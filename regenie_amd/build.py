@@ -15,7 +15,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "librg_step1_hip.so")
 SOURCES = ["rg_api.hip", "bed_prep.hip", "gram_i8.hip", "gram_fp4.hip", "assemble.hip", "chol.hip", "pred.hip", "l1.hip", "ubench.hip", "loocv.hip", "loocv_tri.hip", "l1x.hip", "l0_f64.hip", "step2_qt.hip", "step2_bt.hip", "step2_mcc.hip", "step2_group.hip", "rg_group.hip", "pred_i8.hip", "xy_i8.hip", "wgram_bf16.hip", "bgen_inflate.hip", "ld_corr.hip",
            "pgen_api.cpp", "bgen_api.cpp"]  # host-only: .pgen input (include/rg_pgen.h), BGEN v1.2 input (include/rg_bgen.h)
-HOST_SOURCES = ["driver_common.cpp", "driver_models.cpp", "driver_inputs.cpp", "driver_step2.cpp", "driver_step2_bgen.cpp", "driver_ld.cpp", "driver_step1.cpp", "driver_main.cpp"]  # regenie-amd (host/driver.h)
+HOST_SOURCES = ["driver_common.cpp", "driver_models.cpp", "driver_inputs.cpp", "driver_step2.cpp", "driver_step2_bgen.cpp", "driver_ld.cpp", "driver_step1_plan.cpp", "driver_step1_ingest.cpp", "driver_step1.cpp", "driver_main.cpp"]  # regenie-amd (host/driver.h)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result", "-Wno-inline-asm"]
 
@@ -64,7 +64,7 @@ def kernel_file_digests() -> dict:
 
 
 def _deps():
-    return _lib_deps() + [os.path.join(HERE, "host", f) for f in HOST_SOURCES + ["driver.h", "driver_step2.h", "driver_ld.h", "fmt_g6.h"]]
+    return _lib_deps() + [os.path.join(HERE, "host", f) for f in HOST_SOURCES + ["driver.h", "driver_step1.h", "driver_step2.h", "driver_ld.h", "fmt_g6.h"]]
 
 
 def _lib_deps():

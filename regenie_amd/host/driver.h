@@ -21,7 +21,10 @@
 //   driver_step2.cpp   `--step 2`: single-variant tests on the rg_step2.h kernels, one part per GPU (driver_step2.h: what it shares with the next)
 //   driver_step2_bgen.cpp  the BGEN read-ahead of `--step 2` (BgenAhead), the planning of its groups
 //   driver_ld.cpp      `--step 2 --compute-corr`: the LD matrix of a region on the rg_ld.h kernels
-//   driver_step1.cpp   `--step 1`: streamed ingest, level 0, the multi-GPU exchange, level 1, the .loco / .prs writers; run()
+//   driver_step1_plan.cpp    `--step 1` without a device: the plan of a run (blocks, folds, ridge grids, penalties, GPU ranges), `--split-l0`, the
+//                            .loco / .prs / .firth writer and the lists (driver_step1.h: what the Step-1 units share)
+//   driver_step1_ingest.cpp  `--step 1`: the genotype ingest under one owner (mapped .bed, its copy in device memory, the ring of host buffers)
+//   driver_step1.cpp   `--step 1`: contexts, level 0, the multi-GPU exchange, level 1, the level-0 job files; run()
 //   driver_main.cpp    main()
 #pragma once
 #include <algorithm>

@@ -65,7 +65,7 @@ def test_cli_matches_oracle_files(example_dir, tmp_path):
 
 @pytest.mark.parametrize("stage", ["1", "2", "given_up"])
 def test_cli_bed_staged_in_device_memory_equals_streamed(example_dir, tmp_path, stage):
-    """The whole .bed copied to the device up front (BedStage of host/driver_step1.cpp over rg_stage_alloc / rg_stage_copy; the default for
+    """The whole .bed copied to the device up front (BedStage of host/driver_step1_ingest.cpp over rg_stage_alloc / rg_stage_copy; the default for
     files of several GB, forced here: RG_INGEST_STAGE=1 the pread threads + page-locked ring, =2 pageable copies from the mapping) and level
     0 reading the rows in place must give the files of the batch-by-batch ingest byte for byte."""
     E = example_dir
@@ -86,6 +86,25 @@ def test_cli_bed_staged_in_device_memory_equals_streamed(example_dir, tmp_path, 
     assert "copied to the GPU from the mapped file" in outs["streamed"]
     for k in (1, 2):
         assert open(str(tmp_path / ("staged_%d.loco" % k)), "rb").read() == open(str(tmp_path / ("streamed_%d.loco" % k)), "rb").read()
+
+
+def test_cli_bed_host_ring_equals_mapped(example_dir, tmp_path):
+    """RG_INGEST_MAP=0: a .bed run on one GPU takes the ring of host buffers whose page-locking starts under the parsing of the text files (the
+    pre-started IngestRing of host/driver_step1_ingest.cpp, fed by the reader thread); its files must be those of the default mapped route."""
+    E = example_dir
+    common = ["--step", "1", "--bed", os.path.join(E, "example_3chr"), "--phenoFile", os.path.join(E, "phenotype.txt"),
+              "--covarFile", os.path.join(E, "covariates.txt"), "--bsize", "100"]
+    outs = {}
+    for name, env in (("mapped", {}), ("ring", {"RG_INGEST_MAP": "0"})):
+        r = subprocess.run([BIN] + common + ["--out", str(tmp_path / name)], cwd=str(tmp_path), capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, RG_TEARDOWN="1", **env))
+        assert r.returncode == 0, r.stdout + r.stderr
+        outs[name] = r.stdout
+    assert "copied to the GPU from the mapped file" in outs["mapped"]
+    assert "in the reader thread, queued on the GPU after" in outs["ring"] and "mapped file" not in outs["ring"]
+    for k in (1, 2):
+        a = open(str(tmp_path / ("ring_%d.loco" % k)), "rb").read()
+        assert len(a) > 1000 and a == open(str(tmp_path / ("mapped_%d.loco" % k)), "rb").read()
 
 
 def test_cli_embedded_right_hand_sides_equal_separate_rows(example_dir, tmp_path):

@@ -5,7 +5,8 @@
  *     LD = G^T G - (G^T X)(G^T X)^T        G [n][M] hard calls, every variant mean-imputed (mean_impute_g, Data.cpp:4278-4279),
  *                                          X [n][C] the orthonormal covariate basis (new_cov, intercept included)
  * then the reference's treatment of the diagonal and the scaling to correlations (Data.cpp:4386-4397), and the 16-bit R^2
- * quantisation of the binary file (Data.cpp:4431-4436).
+ * quantisation of the binary file (Data.cpp:4431-4436); or, for --skip-scaleG, the unscaled matrix after the diagonal rules
+ * (Data.cpp:4400) and its sparse form under --sparse-thr (Data.cpp:4407-4421), thresholded on the device.
  *
  * How: with g0 = the call with 0 at a missing entry, miss = its indicator and m_j the mean of the observed calls of variant j,
  *     sum_s g_i g_j = A_ij + m_j B_ij + m_i B_ji + m_i m_j D_ij,    A = g0 g0^T,  B_ij = sum_s g0_i miss_j,  D = miss miss^T
@@ -37,10 +38,11 @@ typedef struct rg_ld_ctx rg_ld_ctx;
 #define RG_LD_ERR_ARG (-1)
 #define RG_LD_ERR_HIP (-2)
 
-/* the three forms rg_ld_finish returns */
+/* the four forms rg_ld_finish returns */
 #define RG_LD_R2_U16 0   /* uint16 [M (M - 1) / 2]: r * r * 65535 + 0.5 truncated, row-major over i < j (the binary .corr body) */
 #define RG_LD_CORR_F64 1 /* double [M][M]: the correlation matrix (the text .corr)                                             */
 #define RG_LD_COV_F64 2  /* double [M][M]: LD before the diagonal is looked at and before scaling                               */
+#define RG_LD_GTG_F64 3  /* double [M][M]: LD unscaled after the two diagonal rules (--skip-scaleG: Data.cpp:4118 / :4400)          */
 
 /* n analysed samples (1 <= n < 2^29), C covariate basis columns (intercept included; 1 <= C <= 64), M columns of the matrix
  * (1 <= M <= 2^19; the M x M results and sums must fit the device: 8 M^2 bytes for LD, 4 M^2 per integer sum).  The packed rows
@@ -70,11 +72,23 @@ int rg_ld_append(rg_ld_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, in
  * it; a later call at a scale with another plane count replaces it. */
 int rg_ld_append_int(rg_ld_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int32_t scale, const int32_t* cols);
 
-/* The result in one of the three forms; out is a host pointer, or a device pointer when out_on_device (the quantisation runs on the
+/* The result in one of the four forms; out is a host pointer, or a device pointer when out_on_device (the quantisation runs on the
  * device either way: M (M - 1) bytes leave it, not 8 M^2).  tol: a diagonal entry in (-tol, 0) zeroes its row and column
  * (params.tol = 1e-8); numtol: a non-positive diagonal entry becomes numtol (params.numtol = 1e-6) -- Data.cpp:4386-4397.
+ * RG_LD_GTG_F64 keeps the zeroing rule and then sets diag = max(diag, numtol); nothing is scaled.
  * Every column must have been appended or forced. */
 int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol);
+
+/* The sparse form of the unscaled matrix (--skip-scaleG --sparse-thr, Data.cpp:4407-4421): sd [M] (host) = sqrt of the diagonal of
+ * RG_LD_GTG_F64, and the entries v = LD[i][j] / sd[i] / sd[j] over i < j (LD after the zeroing rule, the two divisions as written)
+ * with fabs(v) >= thr, in row-major order of (i, j); *count is their number.  The M x M matrix is thresholded where it lies: the
+ * triplets stay in device memory, owned by the context, until the next rg_ld_finish_sparse or rg_ld_destroy, and
+ * rg_ld_sparse_fetch copies them out.  Count and order are the same from run to run.  thr must lie in (0, 1): anything else is
+ * RG_LD_ERR_ARG; a triplet buffer (16 bytes per entry) that does not fit the device is RG_LD_ERR_HIP, and the message names the count. */
+int rg_ld_finish_sparse(rg_ld_ctx* ctx, double thr, double tol, double numtol, double* sd, int64_t* count);
+
+/* The triplets of the last rg_ld_finish_sparse: row, col (0-based, row < col) and val, each [count] on the host. */
+int rg_ld_sparse_fetch(rg_ld_ctx* ctx, int32_t* row, int32_t* col, double* val);
 
 /* Test entry: the raw integer sums of one panel pair, rows [a0, a0 + na) against rows [b0, b0 + nb) in the order they were
  * appended (no basis needed): A[i][j] = sum g0_i g0_j, B[i][j] = sum g0_i miss_j, Bt[i][j] = sum miss_i g0_j, D[i][j] = sum miss_i miss_j,

@@ -421,6 +421,88 @@ __global__ __launch_bounds__(256) void k_ld_r2(const double* __restrict__ LD, in
   out[k] = (uint16_t)(v < 65535.0 ? (unsigned)v : 65535u);
 }
 
+// ---- the unscaled matrix (--skip-scaleG) and its sparse form (--sparse-thr) -----------------------------------------------------------
+// Data.cpp:4386-4391 and :4400: zero[c] as k_ld_diag; diag[c] = max(diagonal after the zeroing, numtol); sd[c] = sqrt(diag[c])
+__global__ void k_ld_diag_gtg(const double* __restrict__ LD, int M, double tol, double numtol, uint8_t* __restrict__ zero, double* __restrict__ diag,
+                              double* __restrict__ sd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= M) return;
+  const double d = LD[(int64_t)c * M + c];
+  const bool z = d < 0 && fabs(d) < tol;
+  zero[c] = z ? 1 : 0;
+  const double dd = fmax(z ? 0.0 : d, numtol);
+  diag[c] = dd;
+  sd[c] = sqrt(dd);
+}
+
+__global__ __launch_bounds__(256) void k_ld_gtg(const double* __restrict__ LD, int M, const uint8_t* __restrict__ zero, const double* __restrict__ diag,
+                                                double* __restrict__ out) {
+  const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (i >= M || j >= M) return;
+  out[(int64_t)i * M + j] = i == j ? diag[i] : ((zero[i] || zero[j]) ? 0.0 : LD[(int64_t)i * M + j]);
+}
+
+// The one predicate of the count pass and the write pass: v = LD[i][j] / sd[i] / sd[j] (Data.cpp:4417, the divisions as written),
+// kept when fabs(v) >= thr.  ldrow: row i of LD; sdi = sd[i].
+__device__ __forceinline__ bool ld_sparse_keep(const double* __restrict__ ldrow, bool zi, double sdi, const uint8_t* __restrict__ zero,
+                                               const double* __restrict__ sd, int j, double thr, double& v) {
+  const double x = (zi || zero[j]) ? 0.0 : ldrow[j];
+  v = __ddiv_rn(__ddiv_rn(x, sdi), sd[j]);
+  return fabs(v) >= thr;
+}
+
+#define LDS_WAVES 4      // rows per workgroup of the two sparse passes: one 64-lane wavefront per row
+
+// Both passes walk row i over j in (i, M) in steps of 64 columns, lane l at column j0 + l (coalesced along the row); the kept
+// entries of a step are ordered by the prefix popcount of the wavefront's ballot, the steps by a running base: no atomics, so the
+// order is (i, j) row-major and the same from run to run.
+// WRITE false: nrow[i] = kept entries of row i.  WRITE true: off[i] = exclusive scan of nrow; the triplets go to [off[i], off[i + 1]).
+template <bool WRITE>
+__global__ __launch_bounds__(64 * LDS_WAVES) void k_ld_sparse(const double* __restrict__ LD, int M, const uint8_t* __restrict__ zero, const double* __restrict__ sd,
+                                                              double thr, long long* __restrict__ nrow, const long long* __restrict__ off,
+                                                              int32_t* __restrict__ orow, int32_t* __restrict__ ocol, double* __restrict__ oval) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * LDS_WAVES + (threadIdx.x >> 6);      // (uniform over the wavefront)
+  if (i >= M) return;
+  const double* ldrow = LD + (int64_t)i * M;
+  const bool zi = zero[i] != 0;
+  const double sdi = sd[i];
+  long long base = WRITE ? off[i] : 0;
+  for (int j0 = i + 1; j0 < M; j0 += 64) {
+    const int j = j0 + lane;
+    double v = 0.0;
+    const bool keep = j < M && ld_sparse_keep(ldrow, zi, sdi, zero, sd, j, thr, v);
+    const unsigned long long mask = __ballot(keep);
+    if (WRITE && keep) {
+      const long long at = base + __popcll(mask & ((1ull << lane) - 1ull));
+      orow[at] = i;
+      ocol[at] = j;
+      oval[at] = v;
+    }
+    base += __popcll(mask);
+  }
+  if (!WRITE && lane == 0) nrow[i] = base;
+}
+
+// off[0 .. M] = exclusive scan of nrow[0 .. M) (off[M] = the total).  One workgroup: thread t owns the chunk [t * per, (t + 1) * per).
+__global__ __launch_bounds__(256) void k_ld_scan(const long long* __restrict__ nrow, int M, long long* __restrict__ off) {
+  __shared__ long long part[256];
+  const int t = threadIdx.x, per = (M + 255) / 256;
+  const int lo = min(t * per, M), hi = min(lo + per, M);
+  long long s = 0;
+  for (int k = lo; k < hi; ++k) s += nrow[k];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    long long run = 0;
+    for (int k = 0; k < 256; ++k) { const long long x = part[k]; part[k] = run; run += x; }
+    off[M] = run;
+  }
+  __syncthreads();
+  long long run = part[t];
+  for (int k = lo; k < hi; ++k) { off[k] = run; run += nrow[k]; }
+}
+
 }  // namespace
 
 enum { LD_EMPTY = 0, LD_CALLS, LD_INTS };
@@ -442,6 +524,10 @@ struct rg_ld_ctx {
   std::vector<uint8_t> col_state;     // [M] 0: open, 1: appended, 2: forced
   std::vector<double> mean, gx;       // [nrows], [nrows][C]
   std::vector<int32_t> nmiss;         // [nrows]
+  int32_t* sp_row = nullptr;          // the triplets of the last rg_ld_finish_sparse: [sp_count] each, device memory
+  int32_t* sp_col = nullptr;
+  double* sp_val = nullptr;
+  int64_t sp_count = -1;              // -1: no sparse result is held
   double last_ms = 0.0;
   int64_t last_tiles = 0;
   std::string err;
@@ -533,6 +619,17 @@ static void ld_append_commit(rg_ld_ctx* ctx, int32_t bs, const int32_t* cols, co
   ctx->nrows += bs;
 }
 
+// the triplets rg_ld_finish_sparse left in device memory
+static void ld_sparse_release(rg_ld_ctx* ctx) {
+  (void)hipSetDevice(ctx->dev);
+  if (ctx->sp_row) (void)hipFree(ctx->sp_row);
+  if (ctx->sp_col) (void)hipFree(ctx->sp_col);
+  if (ctx->sp_val) (void)hipFree(ctx->sp_val);
+  ctx->sp_row = ctx->sp_col = nullptr;
+  ctx->sp_val = nullptr;
+  ctx->sp_count = -1;
+}
+
 extern "C" {
 
 int rg_ld_create(rg_ld_ctx** out, int device, int64_t n, int32_t n_cov, int32_t n_col) {
@@ -565,6 +662,7 @@ void rg_ld_destroy(rg_ld_ctx* ctx) {
     if (ctx->s2) rg_s2_destroy(ctx->s2);
     if (ctx->rows) (void)hipFree(ctx->rows);
     if (ctx->planes) (void)hipFree(ctx->planes);
+    ld_sparse_release(ctx);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
     if (ctx->e1) (void)hipEventDestroy(ctx->e1);
     (void)hipStreamDestroy(ctx->st);
@@ -710,20 +808,28 @@ int rg_ld_pair_sums(rg_ld_ctx* ctx, int32_t a0, int32_t na, int32_t b0, int32_t 
   return ld_pair_sums<int32_t>(ctx, a0, na, b0, nb, {A, B, Bt, D});
 }
 
-int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol) {
-  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: context was not created");
-  if (!out || (form != RG_LD_R2_U16 && form != RG_LD_CORR_F64 && form != RG_LD_COV_F64) || !(numtol > 0) || !(tol >= 0))
-    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: bad arguments");
-  if (!ctx->s2) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: rg_ld_set_basis has not been called");
+}  // extern "C"
+
+// What rg_ld_finish and rg_ld_finish_sparse share: the checks of the context, then LD [M][M] (both triangles, forced columns zero) into
+// dLD on the context's stream -- the Gram of the panels and the fp64 combination; not synchronised.  started: the Gram kernel ran.
+struct LdBuildTmp {      // what the stream reads until the caller synchronises it
+  DevBuf SA, SB, SD, Tm, Mean, Gx, Col;
+  std::vector<uint8_t> tile_miss;
+};
+
+static int ld_build(rg_ld_ctx* ctx, const std::string& who, DevBuf& dLD, LdBuildTmp& tmp, bool& started) {
+  started = false;
+  if (!ctx->s2) return ld_fail(ctx, RG_LD_ERR_ARG, who + ": rg_ld_set_basis has not been called");
   const int M = ctx->M, R = ctx->nrows, C = ctx->C;
   for (int c = 0; c < M; ++c)
-    if (!ctx->col_state[c]) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: column " + std::to_string(c) + " was neither appended nor forced");
+    if (!ctx->col_state[c]) return ld_fail(ctx, RG_LD_ERR_ARG, who + ": column " + std::to_string(c) + " was neither appended nor forced");
   LD_HIP(hipSetDevice(ctx->dev));
   const int nt = (R + LT - 1) / LT;
-  std::vector<uint8_t> tile_miss(std::max(1, nt), 0);
+  std::vector<uint8_t>& tile_miss = tmp.tile_miss;
+  tile_miss.assign(std::max(1, nt), 0);
   bool any_miss = false;
   for (int r = 0; r < R; ++r) if (ctx->nmiss[r] > 0) { tile_miss[r / LT] = 1; any_miss = true; }
-  DevBuf dLD, dSA, dSB, dSD, dTm, dMean, dGx, dCol, dZero, dInv, dOut;
+  DevBuf &dSA = tmp.SA, &dSB = tmp.SB, &dSD = tmp.SD, &dTm = tmp.Tm, &dMean = tmp.Mean, &dGx = tmp.Gx, &dCol = tmp.Col;
   const size_t MM = (size_t)M * M, RR = (size_t)R * R;
   LD_HIP(dLD.alloc(MM * sizeof(double)));
   LD_HIP(hipMemsetAsync(dLD.p, 0, MM * sizeof(double), ctx->st));
@@ -764,7 +870,33 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
       hipLaunchKernelGGL(k_ld_combine<long long>, g2, dim3(256), 0, ctx->st, dSA.as<long long>(), dSB.as<long long>(), dSD.as<long long>(), R, (double)ctx->scale,
                          dMean.as<double>(), dGx.as<double>(), C, dCol.as<int32_t>(), dLD.as<double>(), M);
     LD_HIP(hipGetLastError());
+    started = true;
   }
+  return RG_LD_OK;
+}
+
+// after the stream of ld_build has been synchronised
+static int ld_build_time(rg_ld_ctx* ctx, bool started) {
+  if (started) {
+    float ms = 0.f;
+    LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+    ctx->last_ms = ms;
+  }
+  return RG_LD_OK;
+}
+
+extern "C" {
+
+int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device, double tol, double numtol) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: context was not created");
+  if (!out || (form != RG_LD_R2_U16 && form != RG_LD_CORR_F64 && form != RG_LD_COV_F64 && form != RG_LD_GTG_F64) || !(numtol > 0) || !(tol >= 0))
+    return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish: bad arguments");
+  const int M = ctx->M;
+  const size_t MM = (size_t)M * M;
+  DevBuf dLD, dZero, dInv, dDiag, dOut;
+  LdBuildTmp tmp;
+  bool started = false;
+  if (int rc = ld_build(ctx, "rg_ld_finish", dLD, tmp, started)) return rc;
   const dim3 gM((M + 15) / 16, (M + 15) / 16);
   const size_t out_bytes = form == RG_LD_R2_U16 ? (size_t)M * (M - 1) / 2 * sizeof(uint16_t) : MM * sizeof(double);
   void* dres = nullptr;
@@ -772,21 +904,89 @@ int rg_ld_finish(rg_ld_ctx* ctx, int32_t form, void* out, int32_t out_on_device,
   else {
     LD_HIP(dZero.alloc(M));
     LD_HIP(dInv.alloc(sizeof(double) * M));
-    hipLaunchKernelGGL(k_ld_diag, dim3((M + 255) / 256), dim3(256), 0, ctx->st, dLD.as<double>(), M, tol, numtol, dZero.as<uint8_t>(), dInv.as<double>());
+    if (form == RG_LD_GTG_F64) {
+      LD_HIP(dDiag.alloc(sizeof(double) * M));
+      hipLaunchKernelGGL(k_ld_diag_gtg, dim3((M + 255) / 256), dim3(256), 0, ctx->st, dLD.as<double>(), M, tol, numtol, dZero.as<uint8_t>(), dDiag.as<double>(),
+                         dInv.as<double>());
+    } else {
+      hipLaunchKernelGGL(k_ld_diag, dim3((M + 255) / 256), dim3(256), 0, ctx->st, dLD.as<double>(), M, tol, numtol, dZero.as<uint8_t>(), dInv.as<double>());
+    }
     LD_HIP(hipGetLastError());
     if (out_on_device) dres = out;
     else { LD_HIP(dOut.alloc(out_bytes)); dres = dOut.p; }
     if (form == RG_LD_CORR_F64) hipLaunchKernelGGL(k_ld_corr, gM, dim3(256), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(), dInv.as<double>(), (double*)dres);
+    else if (form == RG_LD_GTG_F64) hipLaunchKernelGGL(k_ld_gtg, gM, dim3(256), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(), dDiag.as<double>(), (double*)dres);
     else if (M > 1) hipLaunchKernelGGL(k_ld_r2, gM, dim3(256), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(), dInv.as<double>(), (uint16_t*)dres);
     LD_HIP(hipGetLastError());
   }
   if (dres != out && out_bytes > 0) LD_HIP(hipMemcpyAsync(out, dres, out_bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->st));
   LD_HIP(hipStreamSynchronize(ctx->st));
-  if (R > 0) {
-    float ms = 0.f;
-    LD_HIP(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
-    ctx->last_ms = ms;
+  return ld_build_time(ctx, started);
+}
+
+int rg_ld_finish_sparse(rg_ld_ctx* ctx, double thr, double tol, double numtol, double* sd, int64_t* count) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish_sparse: context was not created");
+  if (!sd || !count || !(numtol > 0) || !(tol >= 0)) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish_sparse: bad arguments");
+  if (!(thr > 0 && thr < 1)) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_finish_sparse: the threshold must lie in (0, 1)");
+  ld_sparse_release(ctx);
+  const int M = ctx->M;
+  DevBuf dLD, dZero, dSd, dDiag, dNrow, dOff;
+  long long total = 0;
+  {
+    LdBuildTmp tmp;      // the integer sums are freed before the triplets are allocated
+    bool started = false;
+    if (int rc = ld_build(ctx, "rg_ld_finish_sparse", dLD, tmp, started)) return rc;
+    LD_HIP(dZero.alloc(M));
+    LD_HIP(dSd.alloc(sizeof(double) * M));
+    LD_HIP(dDiag.alloc(sizeof(double) * M));
+    LD_HIP(dNrow.alloc(sizeof(long long) * M));
+    LD_HIP(dOff.alloc(sizeof(long long) * ((size_t)M + 1)));
+    hipLaunchKernelGGL(k_ld_diag_gtg, dim3((M + 255) / 256), dim3(256), 0, ctx->st, dLD.as<double>(), M, tol, numtol, dZero.as<uint8_t>(), dDiag.as<double>(),
+                       dSd.as<double>());
+    LD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ld_sparse<false>, dim3((M + LDS_WAVES - 1) / LDS_WAVES), dim3(64 * LDS_WAVES), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(),
+                       dSd.as<double>(), thr, dNrow.as<long long>(), nullptr, nullptr, nullptr, nullptr);
+    LD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(256), 0, ctx->st, dNrow.as<long long>(), M, dOff.as<long long>());
+    LD_HIP(hipGetLastError());
+    LD_HIP(hipMemcpyAsync(&total, dOff.as<long long>() + M, sizeof(long long), hipMemcpyDeviceToHost, ctx->st));
+    LD_HIP(hipMemcpyAsync(sd, dSd.p, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->st));
+    LD_HIP(hipStreamSynchronize(ctx->st));
+    if (int rc = ld_build_time(ctx, started)) return rc;
   }
+  if (total > 0) {
+    const size_t need = (size_t)total * (2 * sizeof(int32_t) + sizeof(double));
+    size_t free_b = 0, total_b = 0;
+    LD_HIP(hipMemGetInfo(&free_b, &total_b));
+    const bool fits = need <= free_b && hipMalloc((void**)&ctx->sp_row, (size_t)total * sizeof(int32_t)) == hipSuccess &&
+                      hipMalloc((void**)&ctx->sp_col, (size_t)total * sizeof(int32_t)) == hipSuccess &&
+                      hipMalloc((void**)&ctx->sp_val, (size_t)total * sizeof(double)) == hipSuccess;
+    if (!fits) {
+      (void)hipGetLastError();
+      ld_sparse_release(ctx);
+      return ld_fail(ctx, RG_LD_ERR_HIP, "rg_ld_finish_sparse: the " + std::to_string(total) + " entries at or above the threshold need " + std::to_string(need) +
+                                             " bytes of device memory, the device has " + std::to_string(free_b) + " free: raise the threshold");
+    }
+    hipLaunchKernelGGL(k_ld_sparse<true>, dim3((M + LDS_WAVES - 1) / LDS_WAVES), dim3(64 * LDS_WAVES), 0, ctx->st, dLD.as<double>(), M, dZero.as<uint8_t>(),
+                       dSd.as<double>(), thr, nullptr, dOff.as<long long>(), ctx->sp_row, ctx->sp_col, ctx->sp_val);
+    LD_HIP(hipGetLastError());
+    LD_HIP(hipStreamSynchronize(ctx->st));
+  }
+  ctx->sp_count = total;
+  *count = total;
+  return RG_LD_OK;
+}
+
+int rg_ld_sparse_fetch(rg_ld_ctx* ctx, int32_t* row, int32_t* col, double* val) {
+  if (!ctx || !ctx->rows) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_sparse_fetch: context was not created");
+  if (ctx->sp_count < 0) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_sparse_fetch: no sparse result is held (rg_ld_finish_sparse)");
+  if (ctx->sp_count == 0) return RG_LD_OK;
+  if (!row || !col || !val) return ld_fail(ctx, RG_LD_ERR_ARG, "rg_ld_sparse_fetch: null argument");
+  LD_HIP(hipSetDevice(ctx->dev));
+  LD_HIP(hipMemcpyAsync(row, ctx->sp_row, (size_t)ctx->sp_count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipMemcpyAsync(col, ctx->sp_col, (size_t)ctx->sp_count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipMemcpyAsync(val, ctx->sp_val, (size_t)ctx->sp_count * sizeof(double), hipMemcpyDeviceToHost, ctx->st));
+  LD_HIP(hipStreamSynchronize(ctx->st));
   return RG_LD_OK;
 }
 

@@ -76,7 +76,7 @@ EXPORTS = ["rg_create", "rg_destroy", "rg_last_error", "rg_set_problem", "rg_set
            "rg_s2_last_kernel_ms", "rg_s2_qt_moments", "rg_s2_set_coding", "rg_s2_packed_counts", "rg_s2_set_group", "rg_s2_group_counts_packed", "rg_s2_group_sums_int",
            # include/rg_ld.h (the Step-2 LD matrix of a region; wrapped by regenie_amd/ld.py)
            "rg_ld_create", "rg_ld_destroy", "rg_ld_last_error", "rg_ld_set_basis", "rg_ld_force_columns", "rg_ld_append", "rg_ld_append_int", "rg_ld_finish",
-           "rg_ld_pair_sums", "rg_ld_pair_sums_int", "rg_ld_last_kernel_ms", "rg_ld_last_tiles"]
+           "rg_ld_finish_sparse", "rg_ld_sparse_fetch", "rg_ld_pair_sums", "rg_ld_pair_sums_int", "rg_ld_last_kernel_ms", "rg_ld_last_tiles"]
 
 
 def lib_path() -> str:
@@ -232,6 +232,8 @@ def load_library() -> C.CDLL:
     lib.rg_ld_pair_sums_int.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rg_ld_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double]
     lib.rg_ld_pair_sums.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rg_ld_finish_sparse.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.rg_ld_sparse_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rg_ld_last_kernel_ms.argtypes = [C.c_void_p]
     lib.rg_ld_last_kernel_ms.restype = C.c_double
     lib.rg_ld_last_tiles.argtypes = [C.c_void_p]

@@ -118,6 +118,9 @@ struct Params {
   double range_min = 0, range_max = 0;
   // --step 2 --compute-corr: the LD matrix of a region (Data::ld_comp, Data.cpp:3807-3848; driver_ld.cpp)
   bool compute_corr = false, corr_text = false, forcein_vars = false;
+  bool skip_scaleG = false;  // --skip-scaleG: the unscaled matrix (= GtG) with its `M n_samples` header line; text output only
+  bool saw_sparse_thr = false;
+  double sparse_thr = 0;     // --sparse-thr t: its sparse form, the sd line and the `i j r` lines with |r| >= t (0: no sparsifying); needs --skip-scaleG
   bool ld_dosages = false;   // --ld-dosages: the LD matrix of dosage input (--bgen, a .pgen dosage track), Data::compute_ld_dosages; refused without it
   // --step 2 --condition-list FILE [--condition-file FORMAT,FILE [--condition-file-sample FILE]] [--max-condition-vars N]: the listed variants become
   // covariates and leave the tested set (Regenie.cpp:217-219, :277, :516, :714-722; condition_variants in driver_inputs.cpp)

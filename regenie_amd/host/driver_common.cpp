@@ -378,8 +378,14 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--forcein-vars") p.forcein_vars = true;
     else if (a == "--ld-dosages") p.ld_dosages = true;
     else if (a == "--ld-extract") { need(i); usage_error("--ld-extract (burden masks in the LD matrix) is not built: use --extract [--forcein-vars] for single variants."); }
-    else if (a == "--skip-scaleG") usage_error("--skip-scaleG (the LD matrix of unscaled genotypes) is not built.");
-    else if (a == "--sparse-thr") { need(i); usage_error("--sparse-thr (the sparsified LD matrix, which needs --skip-scaleG) is not built."); }
+    else if (a == "--skip-scaleG") p.skip_scaleG = true;                                     // Regenie.cpp:525
+    else if (a == "--sparse-thr") {                                                          // Regenie.cpp:301 (a FLOAT, default 0)
+      const std::string v = need(i);
+      char* end = nullptr;
+      p.sparse_thr = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != '\0') usage_error("Argument ‘" + v + "’ failed to parse");      // the option parser's own message
+      p.saw_sparse_thr = true;
+    }
     else if (a == "--condition-list") p.condition_list = need(i);                              // Regenie.cpp:217, :516
     else if (a == "--condition-file") {                                                      // Regenie.cpp:714-722
       auto t = split_char(need(i), ',');
@@ -456,6 +462,14 @@ Params parse_args(int argc, char** argv) {
     if (p.forcein_vars && p.extract.size() > 1) usage_error("cannot have multiple extract files");      // Geno.cpp:1352
     p.forcein_vars = p.forcein_vars && !p.extract.empty();
   }
+  if (p.saw_sparse_thr) {        // Regenie.cpp:919-924
+    if (!p.skip_scaleG)
+      usage_error("--sparse-thr (the sparsified LD matrix, which needs --skip-scaleG) is not built without --skip-scaleG (regenie: \"cannot use --sparse-thr without --skip-scaleG\").");
+    if (!(p.sparse_thr >= 0 && p.sparse_thr < 1)) usage_error("invalid value passed in --sparse-thr (must be in [0,1)");
+  }
+  if (p.skip_scaleG && !p.compute_corr) usage_error("--skip-scaleG goes with --compute-corr / --output-corr-text.");
+  if (p.skip_scaleG && !p.corr_text)      // (with --sparse-thr the reference writes its text lines into the file it opened in binary mode)
+    usage_error("--skip-scaleG (the LD matrix of unscaled genotypes) is not built for the binary .corr file, whose 16-bit R^2 body has no meaning for unscaled values: add --output-corr-text.");
   if (p.par_set) {               // check_build_code (Regenie.cpp:1643-1660), which the reference runs in test mode
     if (p.step != 2) usage_error("can only use --par-region in step 2 (association testing).");
     const std::string& b = p.build_code;

@@ -2,9 +2,10 @@
 //
 // The host keeps what the reference's host does around print_ld: which variant takes which column (check_in_map_from_files /
 // check_ld_list, Geno.cpp:1343-1380, :1443-1453), the variant lists (write_snplist, Data.cpp:3862-3885), reading the 2-bit rows in
-// panels of --bsize (or, for --bgen and .pgen dosages, the exact integer dosages as uint16 rows), the two output formats.
+// panels of --bsize (or, for --bgen and .pgen dosages, the exact integer dosages as uint16 rows), the output formats (binary R^2, text,
+// and under --skip-scaleG the unscaled text matrix or its --sparse-thr triplets).
 // Everything numeric -- the integer Gram of the panels, the covariate projection, the
-// diagonal rules, the scaling and the 16-bit quantisation -- is the library's (include/rg_ld.h); there is no CPU path.
+// diagonal rules, the scaling, the 16-bit quantisation and the sparse threshold -- is the library's (include/rg_ld.h); there is no CPU path.
 #include "driver_ld.h"
 #include "driver_step2.h"
 
@@ -86,7 +87,7 @@ struct LdCommon {
 class DosagePanels {
  public:
   explicit DosagePanels(const LdCommon& cm) : cm_(cm), r_(cm.r) {
-    sout << "** Computing LD matrix **\n";
+    sout << "** Computing LD matrix " << (cm.p.skip_scaleG ? "(=GtG) " : "") << "**\n";      // Data.cpp:3919
     if (cm.npanels > 0) sout << "  -> splitting across " << cm.npanels << " SV blocks\n";
     if (!r_.bgenh) return;
     if (rg_bgen_block_bytes(r_.bgenh, &block_bytes_) != RG_BGEN_OK) throw std::runtime_error(rg_bgen_last_error(r_.bgenh));
@@ -229,10 +230,14 @@ static void write_snplist(const LdCommon& cm) {
 
 constexpr double LD_TOL = 1e-8;      // params.tol, Regenie.hpp:226
 
+// the first line of the text file under --skip-scaleG (setup_output, Data.cpp:1992): number of columns, params.n_samples
+static std::string gtg_header(const LdCommon& cm) { return std::to_string(cm.M) + " " + std::to_string(cm.r.N) + "\n"; }
+
+// the dense text matrix: correlations, or under --skip-scaleG the header line and the unscaled matrix after the diagonal rules
 static void write_corr_text(const LdCommon& cm) {
   const int64_t M = cm.M;
   std::vector<double> R((size_t)M * M);
-  cm.check(rg_ld_finish(cm.ld, RG_LD_CORR_F64, R.data(), 0, LD_TOL, NUMTOL));
+  cm.check(rg_ld_finish(cm.ld, cm.p.skip_scaleG ? RG_LD_GTG_F64 : RG_LD_CORR_F64, R.data(), 0, LD_TOL, NUMTOL));
   sout << "\n** writing to file **\n";
   std::vector<std::string> lines((size_t)M);
   parallel_for((int)M, cm.nthreads, [&](int i) {
@@ -242,9 +247,39 @@ static void write_corr_text(const LdCommon& cm) {
   });
   std::ofstream f(cm.out);
   if (!f) throw std::runtime_error("cannot write file : " + cm.out);
+  if (cm.p.skip_scaleG) f << gtg_header(cm);
   for (int64_t i = 0; i < M; ++i) { if (i) f << "\n"; f << lines[i]; }      // IOFormat(..., " ", "\n", "", "", "", ""): no newline at the end
   f.flush();
   if (!f) throw std::runtime_error("error while writing file : " + cm.out + " (disk full?)");
+}
+
+// --skip-scaleG --sparse-thr t (Data.cpp:4407-4421): the header line, the M standard deviations on one line, then `i j r` (1-based) per
+// pair i < j with |r| >= t, in row-major order.  The matrix is thresholded on the device; only the triplets come back.
+static void write_corr_sparse(const LdCommon& cm) {
+  const int64_t M = cm.M;
+  std::vector<double> sd((size_t)M);
+  int64_t count = 0;
+  cm.check(rg_ld_finish_sparse(cm.ld, cm.p.sparse_thr, LD_TOL, NUMTOL, sd.data(), &count));
+  std::vector<int32_t> row((size_t)count), col((size_t)count);
+  std::vector<double> val((size_t)count);
+  cm.check(rg_ld_sparse_fetch(cm.ld, row.data(), col.data(), val.data()));
+  sout << "\n** writing to file **\n";
+  std::ofstream f(cm.out);
+  if (!f) throw std::runtime_error("cannot write file : " + cm.out);
+  std::string s = gtg_header(cm);
+  for (int64_t c = 0; c < M; ++c) { if (c) s.push_back(' '); fmt_sig6(sd[c], s); }
+  s.push_back('\n');
+  f << s;
+  char buf[80];
+  s.clear();
+  for (int64_t k = 0; k < count; ++k) {      // (the stream's default format of a double is %g)
+    s.append(buf, (size_t)snprintf(buf, sizeof(buf), "%d %d %g\n", row[k] + 1, col[k] + 1, val[k]));
+    if (s.size() > (1u << 20)) { f << s; s.clear(); }
+  }
+  f << s;
+  f.flush();
+  if (!f) throw std::runtime_error("error while writing file : " + cm.out + " (disk full?)");
+  sout << "  + " << count << " pairs at or above the threshold " << cm.p.sparse_thr << "\n";
 }
 
 static void write_corr_binary(const LdCommon& cm) {
@@ -276,10 +311,11 @@ static int run_ld(Run& r, std::chrono::steady_clock::time_point t_start) {
     DosagePanels(cm).append_all();
   } else {
     append_hard_call_panels(cm);
-    sout << "\n** computing LD matrix **\n";
+    sout << "\n** computing LD matrix " << (p.skip_scaleG ? "(=GtG) " : "") << "**\n";      // Data.cpp:4374
   }
   write_snplist(cm);
-  if (p.corr_text) write_corr_text(cm);
+  if (p.skip_scaleG && p.sparse_thr > 0) write_corr_sparse(cm);      // (--sparse-thr 0: no sparsifying)
+  else if (p.corr_text) write_corr_text(cm);
   else write_corr_binary(cm);
   sout << " -> Gram kernel " << rg_ld_last_kernel_ms(cm.ld) << " ms (" << rg_ld_last_tiles(cm.ld) << " tiles of 128 x 128 over " << cm.sm.n << " samples)\n";
   sout << "\nElapsed time : " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() << "s\nEnd of run\n";

@@ -9,7 +9,7 @@ import numpy as np
 
 from .engine import RgError, load_library
 
-R2_U16, CORR_F64, COV_F64 = 0, 1, 2
+R2_U16, CORR_F64, COV_F64, GTG_F64 = 0, 1, 2, 3
 
 
 def pack_bed_rows(G: np.ndarray) -> np.ndarray:
@@ -111,11 +111,24 @@ class LDMatrix:
         self._check(self.lib.rg_ld_append_int(self.h, ptr, ld, bs, on_device, int(scale), cols.ctypes.data))
 
     def finish(self, form: int = CORR_F64, tol: float = TOL, numtol: float = NUMTOL) -> np.ndarray:
-        """R2_U16 -> uint16 [M (M - 1) / 2] (the binary .corr body, quantised on the device); CORR_F64 / COV_F64 -> float64 [M][M]."""
+        """R2_U16 -> uint16 [M (M - 1) / 2] (the binary .corr body, quantised on the device); CORR_F64 / COV_F64 / GTG_F64 -> float64 [M][M]
+        (GTG_F64: the unscaled matrix after print_ld's two diagonal rules, `--skip-scaleG`)."""
         M = self.M
         out = np.empty(M * (M - 1) // 2, np.uint16) if form == R2_U16 else np.empty((M, M), np.float64)
         self._check(self.lib.rg_ld_finish(self.h, int(form), out.ctypes.data if out.size else C.c_void_p(8), 0, float(tol), float(numtol)))
         return out
+
+    def finish_sparse(self, thr: float, tol: float = TOL, numtol: float = NUMTOL):
+        """`--skip-scaleG --sparse-thr thr` (Data.cpp:4407-4421), thresholded on the device: -> sd float64 [M] (sqrt of the diagonal of
+        GTG_F64) and the triplets row, col (int32, 0-based, row < col) and val = LD[row][col] / sd[row] / sd[col] with |val| >= thr, in
+        row-major order.  Only the triplets leave the device."""
+        sd = np.empty(self.M, np.float64)
+        count = C.c_int64(0)
+        self._check(self.lib.rg_ld_finish_sparse(self.h, float(thr), float(tol), float(numtol), sd.ctypes.data, C.byref(count)))
+        k = int(count.value)
+        row, col, val = np.empty(k, np.int32), np.empty(k, np.int32), np.empty(k, np.float64)
+        self._check(self.lib.rg_ld_sparse_fetch(self.h, row.ctypes.data, col.ctypes.data, val.ctypes.data))
+        return sd, row, col, val
 
     def pair_sums(self, a0: int, na: int, b0: int, nb: int) -> dict:
         """Raw integer sums of rows [a0, a0 + na) against rows [b0, b0 + nb) in append order: A = g0 . g0, B = g0 . miss, Bt = miss . g0, D = miss . miss."""

@@ -9,7 +9,13 @@ of them missing) and appended in place through append_int; --driver then writes 
 and times `--compute-corr --ld-dosages`.  The effective rate 2 * 128^2 * n * tiles / time counts one multiply-add per sample pair of
 a tile whatever the number of digit planes: the figure to hold against an fp64 matrix-core Gram.
 
-  python tools/ld_probe.py --n 200000 --M 4096 [--miss 0.01] [--bsize 1024] [--dosage SCALE] [--driver DIR --ref-threads 16]"""
+With --sparse THR every repetition also times the two routes to the sparse form of the unscaled matrix (`--skip-scaleG --sparse-thr THR`)
+on the panels it holds: the device route, finish_sparse (Gram, diagonal rules, count pass, scan, write pass, the triplets to the host),
+and the host route that was the only one before it, finish(COV_F64) (Gram, the 8 M^2-byte matrix to the host) followed by numpy
+applying the diagonal rules and the same predicate row by row over the upper triangle.  Both routes repeat the Gram; its kernel time
+is printed beside them.  The two entry counts must agree.
+
+  python tools/ld_probe.py --n 200000 --M 4096 [--miss 0.01] [--bsize 1024] [--dosage SCALE] [--sparse THR] [--driver DIR --ref-threads 16]"""
 import argparse
 import json
 import os
@@ -23,6 +29,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def sparse_routes(ld, thr, cov_form):
+    """The device route and the host route to the sparse form at threshold thr, timed with a host clock (both end synchronised)."""
+    t0 = time.perf_counter()
+    sd, row, col, val = ld.finish_sparse(thr)
+    t1 = time.perf_counter()
+    gram_dev = ld.kernel_ms
+    cov = ld.finish(cov_form)
+    t2 = time.perf_counter()
+    gram_host = ld.kernel_ms
+    d = np.diag(cov).copy()      # print_ld's two diagonal rules, then the predicate of Data.cpp:4417-4418 row by row
+    zero = (d < 0) & (np.abs(d) < ld.TOL)
+    cov[zero, :] = 0
+    cov[:, zero] = 0
+    hsd = np.sqrt(np.maximum(np.where(zero, 0.0, d), ld.NUMTOL))
+    hrow, hcol, hval = [], [], []
+    for i in range(ld.M - 1):
+        v = cov[i, i + 1:] / hsd[i] / hsd[i + 1:]
+        k = np.nonzero(np.abs(v) >= thr)[0]
+        if k.size:
+            hrow.append(np.full(k.size, i, np.int32))
+            hcol.append((k + i + 1).astype(np.int32))
+            hval.append(v[k])
+    hcount = int(sum(x.size for x in hrow))
+    t3 = time.perf_counter()
+    same = hcount == len(row) and (hcount == 0 or (np.array_equal(np.concatenate(hrow), row) and np.array_equal(np.concatenate(hcol), col)))
+    return {"thr": thr, "entries": int(len(row)), "host_entries": hcount, "same_pairs": bool(same),
+            "device_route_s": t1 - t0, "device_route_gram_ms": gram_dev,
+            "host_route_s": t3 - t1, "host_route_cov_to_host_s": t2 - t1, "host_route_threshold_s": t3 - t2, "host_route_gram_ms": gram_host,
+            "matrix_bytes": 8 * ld.M * ld.M, "triplet_bytes": 16 * int(len(row))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=200000)
@@ -32,13 +69,14 @@ def main():
     ap.add_argument("--bsize", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--dosage", type=int, default=0)
+    ap.add_argument("--sparse", type=float, default=0.0)
     ap.add_argument("--driver", default=None)
     ap.add_argument("--ref-threads", type=int, default=16)
     ap.add_argument("--ref-timeout", type=int, default=600)
     a = ap.parse_args()
     import torch
     torch.cuda.init()
-    from regenie_amd.ld import R2_U16, LDMatrix
+    from regenie_amd.ld import COV_F64, R2_U16, LDMatrix
     n, M, nb = a.n, a.M, (a.n + 3) // 4
     rng = np.random.default_rng(1)
     X = np.linalg.qr(np.column_stack([np.ones(n), rng.normal(size=(n, a.C - 1))]))[0]
@@ -80,6 +118,7 @@ def main():
             ld.finish(R2_U16)
             t2 = time.perf_counter()
             ms, tiles = ld.kernel_ms, ld.tiles
+            sparse = sparse_routes(ld, a.sparse, COV_F64) if a.sparse > 0 else None
         ops = 2.0 * tiles * 128 * 128 * ((n + 63) // 64 * 64)
         run = {"append_s": t1 - t0, "finish_s": t2 - t1, "gram_ms": ms, "tiles": tiles, "gram_int_ops_per_s": ops / (ms * 1e-3)}
         if a.dosage:      # `tiles` counts 128 x 128 sums (A, B, Bt, D); an A tile runs nprod^2 plane products, a B tile nprod, a D tile one
@@ -90,6 +129,8 @@ def main():
             run["gram_int_ops_per_s"] = 2.0 * products * 128 * 128 * ((n + 63) // 64 * 64) / (ms * 1e-3)
             run["effective_ops_per_s"] = 2.0 * tiles * 128 * 128 * n / (ms * 1e-3)
             run["plane_products"] = products
+        if sparse:
+            run["sparse"] = sparse
         res["runs"].append(run)
     if a.driver and a.dosage:
         import struct

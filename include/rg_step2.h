@@ -231,7 +231,30 @@ int rg_s2_set_group(rg_s2_ctx* ctx, const uint8_t* member, const uint8_t* mask);
 int rg_s2_group_counts_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, int32_t* counts);
 int rg_s2_group_sums_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int64_t* sums);
 
-/* Device time of the kernels of the last rg_s2_qt_block / rg_s2_qt_block_packed / rg_s2_qt_moments call (hipEvents on the library's stream), in ms. */
+/* ---- quantitative traits: two-stage rank-inverse-normal transformation of the residuals (`--apply-rerint`, `--apply-rerint-cov`; csrc/step2_rerint.hip) ---
+ * Data::residualize_res (Data.cpp:2407-2436; Sofer et al. 2020: RN-Resid-Unadj / RN-Resid-Adj) and the tail of compute_res (:2397-2400), once per
+ * chromosome: the caller hands rg_s2_set_null the MASKED, UNSCALED residuals Y - LOCO prediction (its scf_sv argument is overwritten here), then calls
+ * rg_s2_qt_rerint before the first block.  On the library's stream, in place on the context's residuals, per trait p over its observed samples:
+ *   rank    rint_pheno (Pheno.cpp:1975-2011): a block of tied values starting at sorted position i (0-based) of length m gets (i + 1) + (m - 1) / 2;
+ *           the ranks depend on the values alone, not on the order of the samples (hand-written bitonic sort of order-preserving 64-bit keys)
+ *   y       Phi^-1((rank - kc) / (nvals - 2 kc + 1)), kc = 3 / 8, in fp64 (Wichura's AS241); unobserved samples stay 0
+ *   RG_S2_RERINT_COV only:  beta = res^T X, res -= mask .* (X beta^T)       (fp64, fixed summation order: two calls give the same bytes)
+ *   scale_Y = |res_p| / sqrt(Neff_p - C), 1 where pass[p] == 0; below numtol: the error `some phenotype residuals has sd=0.` (the context then
+ *           has no null model until the next rg_s2_set_null); res /= scale_Y
+ *   p_sd_yres = |res_p| / sqrt(Neff_p - C), res /= p_sd_yres, scf_sv = scale_Y * p_sd_yres replaces the context's  (compute_res)
+ * Neff_p = the observed samples of the mask handed to rg_s2_set_null (more than C of them).  The block entries and rg_s2_qt_moments then run as after
+ * any rg_s2_set_null.  A context on which this is never called allocates and launches nothing of it.  pass: [P] host bytes or NULL (all 1). */
+#define RG_S2_RERINT 1
+#define RG_S2_RERINT_COV 2
+typedef struct rg_s2_rerint_out {   /* HOST pointers, each may be NULL */
+  double* scale_Y;   /* [P]    pheno_data.scale_Y as residualize_res leaves it                              */
+  double* scf_sv;    /* [P]    scale_Y * p_sd_yres: the factor of BETA and SE                                */
+  double* res;       /* [P][n] the residuals the tests will read (transformed, projected, scaled twice)      */
+  double* ranks;     /* [P][n] the ranks (0 for an unobserved sample)                                        */
+} rg_s2_rerint_out;
+int rg_s2_qt_rerint(rg_s2_ctx* ctx, int32_t mode, const uint8_t* pass, double numtol, const rg_s2_rerint_out* out);
+
+/* Device time of the kernels of the last rg_s2_qt_block / rg_s2_qt_block_packed / rg_s2_qt_moments / rg_s2_qt_rerint call (hipEvents on the library's stream), in ms. */
 double rg_s2_last_kernel_ms(const rg_s2_ctx* ctx);
 
 #ifdef __cplusplus

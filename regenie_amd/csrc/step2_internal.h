@@ -86,6 +86,8 @@ struct rg_s2_ctx {
   } last_qt;
   void* mbuf[4] = {nullptr, nullptr, nullptr, nullptr};      // rg_s2_qt_moments: listed rows, partial sums, b, results
   size_t mcap[4] = {0, 0, 0, 0};
+  void* rbuf[4] = {nullptr, nullptr, nullptr, nullptr};      // rg_s2_qt_rerint (step2_rerint.hip): sort keys, ranks, partial sums, per-trait scalars; null until it is called
+  size_t rcap[4] = {0, 0, 0, 0};
   // ---- rg_s2_set_coding (`--test dominant | recessive`): the staged hard-call rows are relabelled after they have been counted ----
   int coding = RG_S2_ADDITIVE;
   int staged_bs = 0;            // rows of the block last staged by a hard-call entry (rg_s2_packed_counts)
@@ -138,3 +140,4 @@ static inline int rg_s2_fetch_trait_counts(rg_s2_ctx* ctx, int bs, std::vector<i
 void rg_s2_bt_free(rg_s2_ctx* ctx);   // step2_bt.hip
 void rg_s2_mcc_free(rg_s2_ctx* ctx);  // step2_mcc.hip
 void rg_s2_group_free(rg_s2_ctx* ctx);  // step2_group.hip
+void rg_s2_rerint_free(rg_s2_ctx* ctx);  // step2_rerint.hip

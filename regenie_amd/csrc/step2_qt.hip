@@ -1341,6 +1341,7 @@ void rg_s2_destroy(rg_s2_ctx* ctx) {
     rg_s2_bt_free(ctx);
     rg_s2_mcc_free(ctx);
     rg_s2_group_free(ctx);
+    rg_s2_rerint_free(ctx);
     if (ctx->e0) (void)hipEventDestroy(ctx->e0);
     if (ctx->e1) (void)hipEventDestroy(ctx->e1);
     (void)hipStreamDestroy(ctx->st);

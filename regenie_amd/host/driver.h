@@ -76,6 +76,9 @@ struct Params {
   std::vector<std::string> keep, remove, extract, exclude, pheno_cols, covar_cols, cat_covar;
   int max_cat_levels = 10;
   bool rint = false;
+  // --apply-rerint / --apply-rerint-cov: the two-stage rank-inverse-normal transformation of the Step-2 residuals of quantitative traits
+  // (Regenie.cpp:433-434, :1251-1252; Data::residualize_res, Data.cpp:2407-2436).  Off under --bt; set but without effect under --ct and in step 1.
+  bool rerint = false, rerintcov = false;
   int bsize = 0, cv_folds = 5, n_ridge_l0 = 5, n_ridge_l1 = 5, nchrom = 23, threads = 0;
   int n_block = 0;                         // --nb: total number of blocks, taken chromosome by chromosome (0: all)
   bool firth = false, firth_approx = false, firth_se = false;   // --firth --approx [--firth-se] (step 2, binary traits)

@@ -288,6 +288,8 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--catCovarList") list(p.cat_covar, need(i));
     else if (a == "--maxCatLevels") p.max_cat_levels = atoi(need(i).c_str());
     else if (a == "--apply-rint") p.rint = true;
+    else if (a == "--apply-rerint") p.rerint = true;
+    else if (a == "--apply-rerint-cov") p.rerintcov = true;
     else if (a == "--keep") list(p.keep, need(i));
     else if (a == "--remove") list(p.remove, need(i));
     else if (a == "--extract") list(p.extract, need(i));
@@ -407,6 +409,10 @@ Params parse_args(int argc, char** argv) {
     else usage_error("unrecognised option '" + a + "'");
   }
   if (p.bt) p.rint = false;  // Regenie.cpp:432
+  // Regenie.cpp:433-434: the two flags are dropped under --bt and under nothing else -- with --ct, and in step 1, they stay set, the check below
+  // still fires, and nothing reads them (only compute_res does, Data.cpp:2393: step 2 of a quantitative trait)
+  if (p.bt) p.rerint = p.rerintcov = false;
+  if (p.rerint && p.rerintcov) usage_error("must select one of the two options, --apply-rerint or --apply-rerint-cov");      // Regenie.cpp:1251-1252
   if (p.step != 1 && p.step != 2) usage_error("specify which mode regenie should be running using option --step.");
   // time-to-event traits (Regenie.cpp:570-587, :1197-1201)
   if (p.t2e && !p.event_cols.empty() && saw_pheno_col) usage_error("You must specify TTE phenotypes using '--phenoColList' (matching in order with events in '--eventColList').");

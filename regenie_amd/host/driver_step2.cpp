@@ -16,6 +16,7 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p)
       if (!r.mask[(size_t)q * N + an[k]]) { has_missing[k] = 1; any_missing = true; }
   glm = p.bt || p.ct;                                 // binary / count traits: the score test of a generalised linear null model
   mcc = r.mcc_test && !glm;                           // --mcc: quantitative traits only (the reference ignores it elsewhere, apart from the log line)
+  rerint = glm ? 0 : p.rerint ? RG_S2_RERINT : p.rerintcov ? RG_S2_RERINT_COV : 0;      // compute_res alone reads the flags (Data.cpp:2393)
   Xc.resize((size_t)C * n); Yc.resize((size_t)P * n); Mc.resize((size_t)P * n);
   for (int c = 0; c < C; ++c) for (int64_t k = 0; k < n; ++k) Xc[(size_t)c * n + k] = r.X[(size_t)c * N + an[k]];
   for (int q = 0; q < P; ++q)
@@ -241,6 +242,10 @@ struct ChromNull {
     for (int q = 0; q < cm.P; ++q) {
       const std::vector<double>& blup = blup_q[q];
       if (cm.glm) { fit_glm(chrom, q, blup); continue; }
+      if (cm.rerint) {      // residualize_res and the scaling run on the device below, on the masked residuals as they are
+        for (int64_t k = 0; k < n; ++k) resc[(size_t)q * n + k] = (cm.Yc[(size_t)q * n + k] - blup[cm.an[k]]) * cm.Mc[(size_t)q * n + k];
+        continue;
+      }
       double ss = 0.0;
       for (int64_t k = 0; k < n; ++k) {
         const double v = (cm.Yc[(size_t)q * n + k] - blup[cm.an[k]]) * cm.Mc[(size_t)q * n + k];
@@ -261,7 +266,13 @@ struct ChromNull {
       rc = rg_s2_bt_set_null(s2, &nm);
     } else {
       rc = rg_s2_set_null(s2, cm.Xc.data(), resc.data(), cm.Mc.data(), scf.data());
-      if (cm.mcc) {
+      if (rc == RG_S2_OK && cm.rerint) {      // residualize_res (Data.cpp:2407-2436) + the scaling of compute_res: the residuals come back as the tests read them
+        rg_s2_rerint_out ro;                  // (every part of a --gpus N run: its own context), scale_Y * p_sd_yres replaces scf_sv
+        memset(&ro, 0, sizeof(ro));
+        ro.scf_sv = scf.data(); ro.res = cm.mcc ? resc.data() : nullptr;
+        rc = rg_s2_qt_rerint(s2, cm.rerint, cm.r.pheno_pass.size() == (size_t)cm.P ? cm.r.pheno_pass.data() : nullptr, 1e-6, &ro);
+      }
+      if (rc == RG_S2_OK && cm.mcc) {
         mcc_traits.resize(cm.P);
         for (int q = 0; q < cm.P; ++q) mcc_traits[q] = mcc_setup_trait(resc.data() + (size_t)q * n, cm.Mc.data() + (size_t)q * n, n, cm.C);
       }

@@ -88,6 +88,7 @@ struct S2Common : SampleMap {
   std::map<int, std::vector<int64_t>> chr_snps; // blocks per chromosome (set_blocks_for_testing: ceil(n_chr / bsize))
   int total_blocks = 0;
   bool glm, mcc, firth, spa, correct, per_trait, show_info, multi, fast_bgen;
+  int rerint = 0;                               // --apply-rerint (RG_S2_RERINT) / --apply-rerint-cov (RG_S2_RERINT_COV), quantitative traits only; 0: off
   double z_thr;
   In in;
   int flip, dscale, nthreads, nt_prep;

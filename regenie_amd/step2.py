@@ -40,7 +40,12 @@ class _MccOut(C.Structure):
     _fields_ = [("sums", C.c_void_p)]
 
 
+class _RerintOut(C.Structure):
+    _fields_ = [("scale_Y", C.c_void_p), ("scf_sv", C.c_void_p), ("res", C.c_void_p), ("ranks", C.c_void_p)]
+
+
 BT_FIRTH_APPROX, BT_SPA = 1, 2
+RERINT, RERINT_COV = 1, 2                    # rg_s2_qt_rerint
 ADDITIVE, DOMINANT, RECESSIVE = 0, 1, 2      # rg_s2_set_coding
 
 
@@ -243,6 +248,19 @@ class Step2QT:
         res = {"sums": np.zeros((variant.size, self.P, 7))}
         out = _MccOut(res["sums"].ctypes.data)
         self._check(self.lib.rg_s2_qt_moments(self.h, variant.size, variant.ctypes.data, C.byref(out)))
+        res["kernel_ms"] = self.lib.rg_s2_last_kernel_ms(self.h)
+        return res
+
+    def rerint(self, mode: int, passed=None, numtol: float = NUMTOL) -> dict:
+        """`--apply-rerint` (mode RERINT) / `--apply-rerint-cov` (RERINT_COV) on the residuals of the last set_null, which must have been handed the
+        masked, UNSCALED residuals Y - LOCO prediction (its scf_sv is replaced).  -> res [P][n] (what the block entries now read), ranks [P][n]
+        (0 = unobserved), scale_Y [P], scf_sv [P] = scale_Y * p_sd_yres.  Raises RgError `some phenotype residuals has sd=0.` for a constant trait."""
+        res = {"res": np.zeros((self.P, self.n)), "ranks": np.zeros((self.P, self.n)), "scale_Y": np.zeros(self.P), "scf_sv": np.zeros(self.P)}
+        ps = None if passed is None else np.ascontiguousarray(np.asarray(passed) != 0, dtype=np.uint8)
+        if ps is not None and ps.shape != (self.P,):
+            raise ValueError("rerint: passed must be [P]")
+        out = _RerintOut(*[res[k].ctypes.data for k in ("scale_Y", "scf_sv", "res", "ranks")])
+        self._check(self.lib.rg_s2_qt_rerint(self.h, int(mode), None if ps is None else ps.ctypes.data, float(numtol), C.byref(out)))
         res["kernel_ms"] = self.lib.rg_s2_last_kernel_ms(self.h)
         return res
 

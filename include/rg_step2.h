@@ -35,7 +35,10 @@ typedef struct rg_s2_ctx rg_s2_ctx;
 #define RG_S2_MAX_COV 64
 #define RG_S2_MAX_PHENO 64
 
-/* n samples in the analysis, C covariate basis columns (intercept included, as in new_cov), P phenotypes. */
+/* n samples in the analysis, C covariate basis columns (intercept included, as in new_cov), P phenotypes; n > C.  C = 0 makes a context without a
+ * covariate basis: the calls that bring a model or columns (rg_s2_set_null, rg_s2_bt_set_null, rg_s2_set_columns), which every score and
+ * contraction entry needs first, refuse it; the count entries of a sample group or of the cases (rg_s2_set_group / rg_s2_set_cases with their
+ * masks handed over) are all it serves, on any n >= 1. */
 int rg_s2_create(rg_s2_ctx** out, int device, int64_t n, int32_t n_cov, int32_t n_pheno);
 void rg_s2_destroy(rg_s2_ctx* ctx);
 const char* rg_s2_last_error(const rg_s2_ctx* ctx);
@@ -230,6 +233,39 @@ int rg_s2_qt_moments(rg_s2_ctx* ctx, int32_t nv, const int32_t* variant, const r
 int rg_s2_set_group(rg_s2_ctx* ctx, const uint8_t* member, const uint8_t* mask);
 int rg_s2_group_counts_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, int32_t* counts);
 int rg_s2_group_sums_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int64_t* sums);
+
+/* ---- allele counts among the cases of each binary trait (`--af-cc`; csrc/step2_group.hip, the same bit planes with a per-trait member) -----------
+ * The reference adds, for every analysed sample whose call at the variant is observed and every trait p, g * mask_p * y_p to af_case[p] and
+ * mask_p * y_p to ns_case[p] (update_af_cc, Geno.cpp:3069-3075; g = the additive call as read, after --ref-first, before imputation, the minor-allele
+ * flip and any recoding; y_p = the 0 / 1 phenotype) and prints A1FREQ_CASES = af_case / (2 ns_case), A1FREQ_CONTROLS = (af - af_case) / (2 ns - 2 ns_case),
+ * N_CASES, N_CONTROLS per trait (compute_aaf_info, :3119-3126).  The division stays with the caller; the sums come from:
+ *   rg_s2_set_cases           is_case [P][n] host bytes (0 / 1; NULL clears the cases).  is_case_p AND mask_p is packed into P bit planes laid out like a
+ *                             2-bit row (no plane 0), by the function that packs the group's, into the same device buffer.  mask [P][n] host bytes, or
+ *                             NULL for the masks of rg_s2_set_null (packed again when that call brings new masks).
+ *   rg_s2_case_counts_packed  2-bit rows as rg_s2_group_counts_packed takes them -> counts [bs][P][3] = calls equal to 1, equal to 2, observed among
+ *                             the observed cases of trait p.  ADDITIVE under every coding (it reads the caller's rows).
+ *   rg_s2_case_sums_int       uint16 rows as rg_s2_group_sums_int takes them -> sums [bs][P][2] int64 = exact sum (units of 1 / scale), observed count.
+ *                             A kernel of its own: a lane loads 16 bytes (eight values) at a time; rows whose address or pitch is no multiple of
+ *                             16 bytes are read value by value.
+ * Exact integers, no atomics: two calls give the same bytes.  When a group is set as well, a case entry makes ONE launch over the 1 + 2 P planes, so
+ * the rows of a block are read once for both sets; the group's part of that launch -- the same numbers rg_s2_group_counts_packed / rg_s2_group_sums_int
+ * would return for those rows -- is kept on the host until the next case entry or set call and handed out by
+ *   rg_s2_group_counts_last   counts [bs][1 + P][3] of the last rg_s2_case_counts_packed
+ *   rg_s2_group_sums_last     sums [bs][1 + P][2] of the last rg_s2_case_sums_int      (an error when there is no such call, no group was set then, or
+ *                             bs is not that call's: the caller's buffer is sized by it).
+ * A case entry given HOST rows copies them to the device once; a caller that scores the same block hands that copy on instead of having the score
+ * entry upload the rows a second time:
+ *   rg_s2_case_rows_staged    *rows = the device copy the last case entry made of its host rows, *ld = its pitch in elements (bytes for 2-bit rows,
+ *                             uint16 for integer rows: a multiple of 8, 16-byte aligned) -- to be passed to a score entry with rows_on_device /
+ *                             g_on_device = 1.  Valid until the next count entry or set call of this context; an error when the last case entry
+ *                             took device rows or there was none.
+ * A context on which rg_s2_set_cases was never called allocates and launches nothing of this; the count entries then return RG_S2_ERR_ARG. */
+int rg_s2_set_cases(rg_s2_ctx* ctx, const uint8_t* is_case, const uint8_t* mask);
+int rg_s2_case_counts_packed(rg_s2_ctx* ctx, const uint8_t* rows, int64_t ld, int32_t bs, int32_t rows_on_device, int32_t flip, int32_t* counts);
+int rg_s2_case_sums_int(rg_s2_ctx* ctx, const uint16_t* G, int64_t ld, int32_t bs, int32_t g_on_device, int64_t* sums);
+int rg_s2_group_counts_last(rg_s2_ctx* ctx, int32_t bs, int32_t* counts);
+int rg_s2_group_sums_last(rg_s2_ctx* ctx, int32_t bs, int64_t* sums);
+int rg_s2_case_rows_staged(rg_s2_ctx* ctx, const void** rows, int64_t* ld);
 
 /* ---- quantitative traits: two-stage rank-inverse-normal transformation of the residuals (`--apply-rerint`, `--apply-rerint-cov`; csrc/step2_rerint.hip) ---
  * Data::residualize_res (Data.cpp:2407-2436; Sofer et al. 2020: RN-Resid-Unadj / RN-Resid-Adj) and the tail of compute_res (:2397-2400), once per

@@ -515,6 +515,7 @@ int rg_s2_bt_set_null(rg_s2_ctx* ctx, const rg_s2_bt_null* nm) {
   if (!ctx || !ctx->st) return rg_s2_fail(ctx, RG_S2_ERR_ARG, "rg_s2_bt_set_null: context was not created");
   if (!nm || !nm->X || !nm->y || !nm->mask || !nm->fitted || nm->family < 0 || nm->family > 1)
     return rg_s2_fail(ctx, RG_S2_ERR_ARG, "rg_s2_bt_set_null: null argument / family must be 0 (binary) or 1 (count)");
+  if (ctx->C < 1) return rg_s2_fail(ctx, RG_S2_ERR_ARG, "rg_s2_bt_set_null: the context was created without a covariate basis (n_cov = 0)");
   S2_HIP(hipSetDevice(ctx->dev));
   if (!ctx->bt) ctx->bt = new BtState();
   BtState& bt = *ctx->bt;

@@ -1282,8 +1282,8 @@ int rg_s2_create(rg_s2_ctx** out, int device, int64_t n, int32_t n_cov, int32_t 
   if (!out) return RG_S2_ERR_ARG;
   rg_s2_ctx* ctx = new rg_s2_ctx();
   *out = ctx;
-  if (n <= 0 || n >= (1 << 26) || n_cov < 1 || n_cov > RG_S2_MAX_COV || n_pheno < 1 || n_pheno > RG_S2_MAX_PHENO || n <= n_cov)
-    return fail(ctx, RG_S2_ERR_ARG, "rg_s2_create: need n > n_cov, 1 <= n_cov <= 64, 1 <= n_pheno <= 64");
+  if (n <= 0 || n >= (1 << 26) || n_cov < 0 || n_cov > RG_S2_MAX_COV || n_pheno < 1 || n_pheno > RG_S2_MAX_PHENO || n <= n_cov)
+    return fail(ctx, RG_S2_ERR_ARG, "rg_s2_create: need n > n_cov, 0 <= n_cov <= 64 (0: a context for the count entries alone), 1 <= n_pheno <= 64");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(ctx, RG_S2_ERR_HIP, "rg_s2_create: no HIP device (this library has no CPU path)");
@@ -1300,7 +1300,7 @@ int rg_s2_create(rg_s2_ctx** out, int device, int64_t n, int32_t n_cov, int32_t 
   S2_HIP(hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking));
   S2_HIP(hipEventCreate(&ctx->e0));
   S2_HIP(hipEventCreate(&ctx->e1));
-  S2_HIP(hipMalloc((void**)&ctx->dX, sizeof(double) * n * n_cov));
+  S2_HIP(hipMalloc((void**)&ctx->dX, sizeof(double) * n * std::max(1, n_cov)));
   S2_HIP(hipMalloc((void**)&ctx->dY, sizeof(double) * n * n_pheno));
   S2_HIP(hipMalloc((void**)&ctx->dM, (size_t)n * n_pheno));
   S2_HIP(hipMalloc((void**)&ctx->dscf, sizeof(double) * n_pheno));
@@ -1354,6 +1354,7 @@ const char* rg_s2_last_error(const rg_s2_ctx* ctx) { return ctx ? ctx->err.c_str
 int rg_s2_set_null(rg_s2_ctx* ctx, const double* X, const double* yres, const uint8_t* mask, const double* scf_sv) {
   if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_null: context was not created");
   if (!X || !yres || !mask || !scf_sv) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_null: null argument");
+  if (ctx->C < 1) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_null: the context was created without a covariate basis (n_cov = 0)");
   S2_HIP(hipSetDevice(ctx->dev));
   ctx->last_qt.kind = 0;      // a scored block belongs to the null model it was scored under
   S2_HIP(hipMemcpyAsync(ctx->dX, X, sizeof(double) * ctx->n * ctx->C, hipMemcpyHostToDevice, ctx->st));
@@ -1770,6 +1771,7 @@ int rg_s2_set_columns(rg_s2_ctx* ctx, int32_t n_col, const double* cols, int32_t
   if (!ctx || !ctx->st) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_columns: context was not created");
   if (!cols || n_col < 1 || n_col > 4096 || n_sq < 0 || n_sq > n_col)
     return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_columns: need 1 <= n_col <= 4096 and 0 <= n_sq <= n_col");
+  if (ctx->C < 1) return fail(ctx, RG_S2_ERR_ARG, "rg_s2_set_columns: the context was created without a covariate basis (n_cov = 0)");
   const int64_t n = ctx->n;
   S2_HIP(hipSetDevice(ctx->dev));
   const int ngrp = (n_col + 15) / 16;

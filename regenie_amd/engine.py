@@ -74,6 +74,7 @@ EXPORTS = ["rg_create", "rg_destroy", "rg_last_error", "rg_set_problem", "rg_set
            # include/rg_step2.h (Step-2 QT score test; wrapped by regenie_amd/step2.py)
            "rg_s2_create", "rg_s2_destroy", "rg_s2_last_error", "rg_s2_set_null", "rg_s2_qt_block", "rg_s2_qt_block_packed", "rg_s2_qt_block_int", "rg_s2_set_sparse_rule", "rg_s2_set_columns", "rg_s2_contract_packed", "rg_s2_contract_int", "rg_s2_bt_set_null", "rg_s2_bt_score_packed", "rg_s2_bt_score_int", "rg_s2_bt_correct",
            "rg_s2_last_kernel_ms", "rg_s2_qt_moments", "rg_s2_set_coding", "rg_s2_packed_counts", "rg_s2_set_group", "rg_s2_group_counts_packed", "rg_s2_group_sums_int", "rg_s2_qt_rerint",
+           "rg_s2_set_cases", "rg_s2_case_counts_packed", "rg_s2_case_sums_int", "rg_s2_group_counts_last", "rg_s2_group_sums_last", "rg_s2_case_rows_staged",
            # include/rg_ld.h (the Step-2 LD matrix of a region; wrapped by regenie_amd/ld.py)
            "rg_ld_create", "rg_ld_destroy", "rg_ld_last_error", "rg_ld_set_basis", "rg_ld_force_columns", "rg_ld_append", "rg_ld_append_int", "rg_ld_finish",
            "rg_ld_finish_sparse", "rg_ld_sparse_fetch", "rg_ld_pair_sums", "rg_ld_pair_sums_int", "rg_ld_last_kernel_ms", "rg_ld_last_tiles"]
@@ -189,6 +190,12 @@ def load_library() -> C.CDLL:
     lib.rg_s2_set_group.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rg_s2_group_counts_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.rg_s2_group_sums_int.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.rg_s2_set_cases.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rg_s2_case_counts_packed.argtypes = lib.rg_s2_group_counts_packed.argtypes
+    lib.rg_s2_case_sums_int.argtypes = lib.rg_s2_group_sums_int.argtypes
+    lib.rg_s2_group_counts_last.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rg_s2_group_sums_last.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.rg_s2_case_rows_staged.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     lib.rg_s2_qt_rerint.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]
     lib.rg_s2_last_kernel_ms.argtypes = [C.c_void_p]
     lib.rg_s2_last_kernel_ms.restype = C.c_double

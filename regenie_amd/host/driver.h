@@ -146,6 +146,9 @@ struct Params {
   bool par_set = false;
   std::string build_code;
   int64_t par1_max = 0, par2_min = 0;
+  // --af-cc (Regenie.cpp:214, :458): A1FREQ_CASES A1FREQ_CONTROLS N_CASES N_CONTROLS in the result files of `--step 2 --bt`; switched off with the
+  // reference's warning in every other mode (:1076-1079)
+  bool af_cc = false;
 };
 
 // a worker thread of a multi-GPU step-2 run logs into its own buffer (tl_log): the parts' logs are appended in order afterwards

@@ -375,6 +375,7 @@ Params parse_args(int argc, char** argv) {
     else if (a == "--par-region") { p.build_code = need(i); p.par_set = true; }            // "build code to identify PAR region boundaries on chrX" (Regenie.cpp:253)
     else if (a == "--skip-dosage-comp") usage_error("--skip-dosage-comp (males' genotypes halved in the tested vector and in A1FREQ outside the PAR regions of chromosome X) is not built.");
     else if (a == "--sex-specific") { need(i); usage_error("--sex-specific (male-only / female-only analyses) is not built."); }
+    else if (a == "--af-cc") p.af_cc = true;                                                 // Regenie.cpp:458
     else if (a == "--compute-corr") p.compute_corr = true;                                   // Regenie.cpp:296-301, :522-535
     else if (a == "--output-corr-text") { p.compute_corr = true; p.corr_text = true; }
     else if (a == "--forcein-vars") p.forcein_vars = true;
@@ -511,6 +512,12 @@ Params parse_args(int argc, char** argv) {
   if (p.write_null_firth && ((p.step == 2 && !(p.firth && p.firth_approx)) || (p.step == 1 && !p.bt))) {   // Regenie.cpp:1218-1222
     std::cout << "WARNING: option --write-null-firth only works for BTs with approximate Firth test.\n";
     p.write_null_firth = false;
+  }
+  // Regenie.cpp:1076-1079: kept only in step 2 for binary traits (the native output split by trait is the only one here); --compute-corr runs with
+  // the default trait mode (quantitative) unless --bt is given, and does not read the flag
+  if (p.af_cc && (p.step != 2 || !p.bt)) {
+    std::cout << "WARNING: disabling option --af-cc (only for BTs in step 2 in native output format split by trait).\n";
+    p.af_cc = false;
   }
   if ((int)!p.bed.empty() + (int)!p.pgen.empty() + (int)!p.bgen.empty() != 1) usage_error("must use either --bed,--bgen or --pgen.");  // Regenie.cpp:419-420
   if (p.pheno_file.empty() && !p.compute_corr) usage_error("option '--phenoFile' is required.");      // Regenie.cpp:1303

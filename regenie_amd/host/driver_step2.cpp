@@ -46,7 +46,15 @@ S2Common::S2Common(Run& r_, const S2Part& part_) : SampleMap(r_), r(r_), p(r_.p)
     for (int64_t k = 0; k < n; ++k) male[k] = (r.sex.size() == (size_t)r.n_file && r.sex[file_idx[k]] == 1) ? 1 : 0;
   }
   // (the device decoder's rows hold the CODED probabilities under --test dominant | recessive: the males' additive sums then come from the general rows)
-  fast_bgen = in == In::Dosage && r.bgenh && (!env.dense || glm) && !(correct && !spa && !p.firth_approx) && !env.bgen_rows && !(sex_aware && coding);
+  af_cc = p.af_cc && p.bt;
+  if (af_cc) {
+    Cc.assign((size_t)P * n, 0); any_case.assign(n, 0);
+    for (int q = 0; q < P; ++q)
+      for (int64_t k = 0; k < n; ++k)
+        if (Mc[(size_t)q * n + k] && Yc[(size_t)q * n + k] == 1.0) { Cc[(size_t)q * n + k] = 1; any_case[k] = 1; }
+  }
+  // (the same for the cases' additive sums of --af-cc)
+  fast_bgen = in == In::Dosage && r.bgenh && (!env.dense || glm) && !(correct && !spa && !p.firth_approx) && !env.bgen_rows && !((sex_aware || af_cc) && coding);
 }
 
 // .bed rows of a block: runs of consecutive variants are cut into pieces read by several threads (the page-cache copy of one pread is a
@@ -300,6 +308,9 @@ struct BlockCounts {
   int P1 = 1;
   std::vector<double> msum;
   std::vector<int64_t> mobs;
+  // --af-cc: the allele total and the observed count among the cases of each trait, [bs][P] (update_af_cc, Geno.cpp:3069-3075)
+  std::vector<double> af_case;
+  std::vector<int64_t> ns_case;
   explicit BlockCounts(int bs) : total(bs, 0.0), ns1(bs, 0), variant_ignored(bs, 0), sum_pos(bs, 0.0), nonpar(bs, 0), het_male(bs, 0) {}
   void mark_non_par(const S2Common& cm, const std::vector<int64_t>& snps, int64_t j0) {
     if (!cm.sex_aware) return;
@@ -384,15 +395,29 @@ struct S2Block {
     if (cm.coding) bc.sum_pos.assign(pb.sum_pos, pb.sum_pos + bs);
     if (cm.per_trait) { bc.af_t.assign(pb.af_t, pb.af_t + bs * P); bc.ns_t.assign(pb.ns_t, pb.ns_t + bs * P); bc.info_t.assign(pb.info_t, pb.info_t + bs * P); }
     integral = true; g16p = pb.g16; g16ld = pb.ld; g16_on_device = pb.on_device;
+    // --af-cc: rows the host threads walked come with their sums among the cases; device-decoded rows never leave the GPU, the library sums them there
+    // (exact integers in units of 1 / scale) -- in the launch that serves the males' planes when the block has a non-PAR variant
+    const bool cases_dev = cm.af_cc && pb.on_device;
+    if (cm.af_cc && !cases_dev) { bc.af_case.assign(pb.af_case, pb.af_case + bs * P); bc.ns_case.assign(pb.ns_case, pb.ns_case + bs * P); }
+    if (cases_dev) fetch_case_sums(bc);
     if (!bc.any_nonpar) return;
-    // the males' sums of the prepared rows (device-decoded rows never leave the GPU): exact integers in units of 1 / scale
+    // the males' sums of the prepared rows
     std::vector<int64_t> gs((size_t)bs * bc.P1 * 2);
-    check(rg_s2_group_sums_int(s2, g16p, g16ld, bs, g16_on_device, gs.data()));
+    check(cases_dev ? rg_s2_group_sums_last(s2, bs, gs.data()) : rg_s2_group_sums_int(s2, g16p, g16ld, bs, g16_on_device, gs.data()));
     for (int j = 0; j < bs; ++j) {
       if (!bc.nonpar[j]) continue;
       for (int q = 0; q < bc.P1; ++q) { bc.msum[(size_t)j * bc.P1 + q] = (double)gs[((size_t)j * bc.P1 + q) * 2] / cm.dscale; bc.mobs[(size_t)j * bc.P1 + q] = gs[((size_t)j * bc.P1 + q) * 2 + 1]; }
       bc.variant_ignored[j] = bc.low_mac(j, cm.p.min_mac) ? 1 : 0;      // (the read-ahead applied the autosomal rule, which never drops what this one keeps)
     }
+  }
+
+  // --af-cc on integer rows: the sums among the cases of each trait from the library (rg_s2_case_sums_int reads the rows the score entry will be given)
+  void fetch_case_sums(BlockCounts& bc) {
+    const size_t P = (size_t)cm.P;
+    std::vector<int64_t> cs((size_t)bs * P * 2);
+    check(rg_s2_case_sums_int(s2, g16p, g16ld, bs, g16_on_device, cs.data()));
+    bc.af_case.resize((size_t)bs * P); bc.ns_case.resize((size_t)bs * P);
+    for (size_t e = 0; e < (size_t)bs * P; ++e) { bc.af_case[e] = (double)cs[2 * e] / cm.dscale; bc.ns_case[e] = cs[2 * e + 1]; }
   }
 
   // route 2, general dosage rows: the analysed samples' doubles, allele totals, the info-score numerator and the per-trait corrections on the
@@ -404,6 +429,10 @@ struct S2Block {
     G.assign((size_t)bs * n, 0.0);
     bc.info_num.assign(bs, 0.0);
     if (cm.per_trait) { bc.af_t.assign((size_t)bs * P, 0.0); bc.ns_t.assign((size_t)bs * P, 0); bc.info_t.assign((size_t)bs * P, 0.0); }
+    // --af-cc: .bgen rows in this loop (their doubles are no integers, the sums are regenie's own in its order; under a coding the uint16 rows hold
+    // the coded values); .pgen dosages -- exact in units of 1 / 16384 -- from the library below
+    const bool cases_here = cm.af_cc && r.bgenh;
+    if (cases_here) { bc.af_case.assign((size_t)bs * P, 0.0); bc.ns_case.assign((size_t)bs * P, 0); }
     parallel_for(bs, cm.nthreads, [&](int j) {
       const double* d = dbuf.data() + (size_t)j * r.n_file;
       const double* iv = r.bgenh ? ibuf.data() + (size_t)j * r.n_file : nullptr;
@@ -423,6 +452,7 @@ struct S2Block {
         tot += v; inf += e; ++ns;
         if (bc.nonpar[j] && cm.male[k]) bc.add_male(cm, j, k, v);
         if (cm.per_trait && cm.has_missing[k]) subtract_masked(cm.Mc.data(), n, P, k, v, e, &bc.af_t[(size_t)j * P], &bc.ns_t[(size_t)j * P], &bc.info_t[(size_t)j * P]);
+        if (cases_here && cm.any_case[k]) add_cases(cm.Cc.data(), n, P, k, v, &bc.af_case[(size_t)j * P], &bc.ns_case[(size_t)j * P]);
       }
       bc.total[j] = tot; bc.ns1[j] = ns; bc.info_num[j] = inf; bc.sum_pos[j] = pos;
       if (bc.low_mac(j, cm.p.min_mac)) bc.variant_ignored[j] = 1;
@@ -446,6 +476,12 @@ struct S2Block {
     });
     for (int j = 0; j < bs; ++j) if (bad[j]) integral = false;
     g16p = G16.data();
+    if (cm.af_cc && !cases_here && integral) {      // the case entry uploads the rows; the score entry reads that device copy in place
+      fetch_case_sums(bc);
+      const void* d = nullptr;
+      check(rg_s2_case_rows_staged(s2, &d, &g16ld));
+      g16p = (const uint16_t*)d; g16_on_device = 1;
+    }
   }
 
   // route 3, hard calls stay packed: the 2-bit codes of the analysed samples go to the device as they are (the rows of the file itself
@@ -496,10 +532,19 @@ struct S2Block {
 
   // hard calls that stayed packed, a block with a non-PAR variant of chromosome X: the males' calls equal to 1, equal to 2 and observed, overall
   // and among each trait's samples, from the library (rg_s2_group_counts_packed reads the rows the score entry was given; additive under every coding)
+  // --af-cc: the same among the cases of each trait (rg_s2_case_counts_packed), first: with a group set its launch covers the males' planes too, the
+  // rows are read once and the males' counts are taken from it
   void fetch_group(BlockCounts& bc) {
+    if (cm.af_cc) {
+      const size_t P = (size_t)cm.P;
+      std::vector<int32_t> cc((size_t)bs * P * 3);
+      check(rg_s2_case_counts_packed(s2, rows, ld, bs, 0, cm.flip, cc.data()));
+      bc.af_case.resize((size_t)bs * P); bc.ns_case.resize((size_t)bs * P);
+      for (size_t e = 0; e < (size_t)bs * P; ++e) { bc.af_case[e] = (double)cc[3 * e] + 2.0 * cc[3 * e + 1]; bc.ns_case[e] = cc[3 * e + 2]; }
+    }
     if (!bc.any_nonpar) return;
     std::vector<int32_t> gc((size_t)bs * bc.P1 * 3);
-    check(rg_s2_group_counts_packed(s2, rows, ld, bs, 0, cm.flip, gc.data()));
+    check(cm.af_cc ? rg_s2_group_counts_last(s2, bs, gc.data()) : rg_s2_group_counts_packed(s2, rows, ld, bs, 0, cm.flip, gc.data()));
     for (int j = 0; j < bs; ++j) {
       if (!bc.nonpar[j]) continue;
       for (int q = 0; q < bc.P1; ++q) {
@@ -624,8 +669,11 @@ struct S2Block {
         if (std::isnan(bc.sum_pos[j])) bc.sum_pos[j] = bt_vstat[(size_t)j * 4] / cm.dscale;
     } else {
       bo.counts = bt_counts.data(); bo.total_p = totp.data(); bo.n_obs_p = nobsp.data();
-      check(rg_s2_bt_score_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &bo));
-      fetch_group(bc);
+      // --af-cc: the case entry goes first and uploads the block; the score entry takes that device copy, so the rows cross PCIe once
+      const void* drows = nullptr; int64_t dld = 0;
+      if (cm.af_cc) { fetch_group(bc); check(rg_s2_case_rows_staged(s2, &drows, &dld)); }
+      if (drows) check(rg_s2_bt_score_packed(s2, (const uint8_t*)drows, dld, bs, 1, cm.flip, NUMTOL, &bo));
+      else { check(rg_s2_bt_score_packed(s2, rows, ld, bs, 0, cm.flip, NUMTOL, &bo)); fetch_group(bc); }
       bc.af_t.assign(totp.begin(), totp.end());      // per-trait allele and sample counts (dosages: the route has them, summed as the reference sums)
       bc.ns_t.assign(nobsp.begin(), nobsp.end());
     }
@@ -734,6 +782,8 @@ struct S2Block {
           double af = total / (2.0 * ns1);
           int64_t nsq = ns1;
           double infq = show_info ? bc.info_num[j] : 0.0;
+          double af_case = 0.0, af_control = 0.0;
+          int64_t ns_case = 0, ns_control = 0;
           if (test_ignored[e]) continue;
           if (cm.per_trait) {   // compute_mac / compute_aaf_info per trait
             const double tq = total + bc.af_t[e];
@@ -741,6 +791,11 @@ struct S2Block {
             if (bc.low_mac_t(j, q, tq, (double)nsq, p.min_mac)) { ++c_tests[t]; continue; }
             af = tq / (2.0 * nsq);
             if (show_info) infq += bc.info_t[e];
+            if (cm.af_cc) {      // compute_aaf_info (Geno.cpp:3119-3126)
+              ns_case = bc.ns_case[e]; ns_control = nsq - ns_case;
+              af_control = (tq - bc.af_case[e]) / (2.0 * nsq - 2.0 * ns_case);
+              af_case = bc.af_case[e] / (2.0 * ns_case);
+            }
           }
           const double info = show_info ? info_score(bgen, infq, (double)nsq, af) : 1.0;
           if (show_info && p.set_min_info && info < p.min_info) { ++c_tests[t]; continue; }     // ignored_trait (Geno.cpp:3143-3144)
@@ -761,8 +816,11 @@ struct S2Block {
           std::ostringstream ln;
           if (af >= 0) ln << head.str() << af << " ";            // print_sum_stats_single (Step2_Models.cpp:2505-2518): a negative value is "NA"
           else ln << head.str() << "NA ";
+          if (cm.af_cc) { if (af >= 0) ln << af_case << " " << af_control << " "; else ln << "NA NA "; }
           if (show_info) { if (info >= 0) ln << info << " "; else ln << "NA "; }      // (the IMPUTE score of very uncertain dosages can be negative)
-          ln << nsq << ' ' << cm.test_name << ' ';
+          ln << nsq;
+          if (cm.af_cc) ln << ' ' << ns_case << ' ' << ns_control;
+          ln << ' ' << cm.test_name << ' ';
           if (se >= 0 && !std::isnan(se)) ln << bh << ' ' << se;
           else ln << "NA NA";
           if (chisq >= 0 && !std::isnan(logp) && !test_fail) ln << ' ' << chisq << ' ' << logp;
@@ -811,6 +869,7 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
            << nm << " analysed males count half in the MAC there\n";
     }
   }
+  if (cm.af_cc) blk.check(rg_s2_set_cases(s2, cm.Cc.data(), cm.Mc.data()));      // (every part of a --gpus N run: its own context)
   sout << std::left << std::setw(20) << " * block size" << ": [" << p.bsize << "]\n";
   sout << std::left << std::setw(20) << " * # blocks" << ": [" << cm.total_blocks << "]\n";
   sout << " * approximate memory usage : n/a (genotype blocks are tested on the GPU)\n";
@@ -823,7 +882,8 @@ int run_step2(Run& r, std::chrono::steady_clock::time_point t_start, S2Part& par
     part.files.push_back(p.out + "_" + r.pheno_names[q] + ".regenie" + (cm.multi ? ".part" + std::to_string(part.part) : (p.gz ? ".gz" : "")));
     ofs.emplace_back(new TextOut(part.files.back(), cm.multi ? false : p.gz));
     if (!*ofs.back()) throw std::runtime_error("cannot write file : " + part.files.back());
-    if (part.part == 0) *ofs.back() << "CHROM GENPOS ID ALLELE0 ALLELE1 A1FREQ " << (cm.show_info ? "INFO " : "") << "N TEST BETA SE CHISQ LOG10P EXTRA\n";
+    if (part.part == 0) *ofs.back() << "CHROM GENPOS ID ALLELE0 ALLELE1 A1FREQ " << (cm.af_cc ? "A1FREQ_CASES A1FREQ_CONTROLS " : "") << (cm.show_info ? "INFO " : "")
+                                          << "N " << (cm.af_cc ? "N_CASES N_CONTROLS " : "") << "TEST BETA SE CHISQ LOG10P EXTRA\n";
   }
   std::unique_ptr<BedAhead> bed(cm.in == In::Bed ? new BedAhead(cm) : nullptr);
   std::unique_ptr<BgenAhead> bgen(cm.fast_bgen ? new BgenAhead(cm) : nullptr);

@@ -98,6 +98,9 @@ struct S2Common : SampleMap {
   // chromosome X outside the pseudo-autosomal regions (--par-region): a male's call counts half in the minor-allele count
   bool sex_aware = false;                       // chromosome X is tested, the sample file has males and --par-region names the bounds
   std::vector<uint8_t> male;                    // per analysed sample: sex code 1 (params->sex subset to the analysis, Geno.cpp:1330-1332)
+  // --af-cc (binary traits): per (trait, analysed sample), 1 = an observed case -- mask_p * y_p of update_af_cc (Geno.cpp:3069-3075)
+  bool af_cc = false;
+  std::vector<uint8_t> Cc, any_case;            // [P][n]; [n]: a case of at least one trait
   bool non_par(int64_t snp) const { return sex_aware && r.snp_chrom[snp] == p.nchrom && r.snp_pos[snp] > p.par1_max && r.snp_pos[snp] < p.par2_min; }   // in_non_par (Geno.cpp:2802-2814)
 };
 
@@ -119,6 +122,11 @@ inline double info_score(bool bgen, double info_num, double ns, double af) {
 inline void subtract_masked(const uint8_t* Mc, int64_t n, int P, int64_t k, double v, double e, double* af_t, int64_t* ns_t, double* info_t) {
   for (int q = 0; q < P; ++q)
     if (!Mc[(size_t)q * n + k]) { af_t[q] -= v; ns_t[q] -= 1; if (info_t) info_t[q] -= e; }
+}
+// update_af_cc (Geno.cpp:3069-3075): sample k's observed additive call v joins the sums of the traits it is a case of
+inline void add_cases(const uint8_t* Cc, int64_t n, int P, int64_t k, double v, double* af_case, int64_t* ns_case) {
+  for (int q = 0; q < P; ++q)
+    if (Cc[(size_t)q * n + k]) { af_case[q] += v; ns_case[q] += 1; }
 }
 // the 2-bit codes of the analysed samples of `bs` rows of the file (bpr bytes each), packed four to a byte; returns the new row length
 inline int64_t repack_analysed(const uint8_t* rows, int64_t bpr, int bs, const int64_t* file_idx, int64_t n, int nthreads, std::vector<uint8_t>& packed) {
@@ -151,6 +159,7 @@ struct PreparedBlock {
   const double *total, *info_num, *af_t, *info_t;       // the *_t: [bs][P], only with S2Common::per_trait
   const double* sum_pos;                                // only with S2Common::coding: the recoded values' sum over the observed samples
   const int64_t *ns1, *ns_t;
+  const double* af_case; const int64_t* ns_case;        // [bs][P], only with S2Common::af_cc and rows the host threads walked (on_device == 0)
   const uint8_t* ignored;
   const uint16_t* g16; int64_t ld; int on_device;
   bool integral;                                        // false: prob0 + prob1 > 1 somewhere in the group, the general route reports what the reference would
@@ -182,6 +191,7 @@ class BgenAhead {
     std::vector<uint8_t> raw, ignored;
     std::vector<double> total, info_num, af_t, info_t, sum_pos;
     std::vector<int64_t> ns1, ns_t;
+    std::vector<double> af_case; std::vector<int64_t> ns_case;      // --af-cc: the host-walked rows' sums among the cases
     bool integral = false;
     double ms_inflate = 0, ms_walk = 0, ms_wall = 0;
     std::string err;

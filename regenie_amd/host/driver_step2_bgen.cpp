@@ -111,6 +111,7 @@ const PreparedBlock* BgenAhead::next_block() {
   v.total = d.total.data() + r0; v.ns1 = d.ns1.data() + r0; v.info_num = d.info_num.data() + r0; v.ignored = d.ignored.data() + r0;
   v.sum_pos = cm_.coding ? d.sum_pos.data() + r0 : nullptr;
   if (cm_.per_trait) { v.af_t = d.af_t.data() + r0 * P; v.ns_t = d.ns_t.data() + r0 * P; v.info_t = d.info_t.data() + r0 * P; }
+  if (cm_.af_cc) { v.af_case = d.af_case.data() + r0 * P; v.ns_case = d.ns_case.data() + r0 * P; }
   v.ld = on_dev ? d.ld_dev : cm_.ld16;
   v.g16 = on_dev ? d.g16_dev + r0 * (size_t)v.ld : d.g16 + (r0 - (size_t)d.host_row0) * (size_t)v.ld;
   v.on_device = on_dev ? 1 : 0;
@@ -209,6 +210,8 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
   const int coding = cm_.coding;
   const int64_t* file_idx = cm_.file_idx.data();
   const uint8_t *has_missing = cm_.has_missing.data(), *Mc = cm_.Mc.data();
+  const bool af_cc = cm_.af_cc;
+  const uint8_t *any_case = cm_.any_case.data(), *Cc = cm_.Cc.data();
   if (lo >= bs) return;
   if (d.g16_rows < bs - lo) {
     if (d.g16) rg_host_free(d.g16);
@@ -237,6 +240,8 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
         af_t = d.af_t.data() + (size_t)j * P; ns_t = d.ns_t.data() + (size_t)j * P; info_t = d.info_t.data() + (size_t)j * P;
         for (int q = 0; q < P; ++q) { af_t[q] = 0.0; ns_t[q] = 0; info_t[q] = 0.0; }
       }
+      double* af_case = af_cc ? d.af_case.data() + (size_t)j * P : nullptr;
+      int64_t* ns_case = af_cc ? d.ns_case.data() + (size_t)j * P : nullptr;
       for (int64_t k = 0; k < n; ++k) {
         const int64_t i = identity ? k : file_idx[k];
         if (ploidy[i] & 0x80) { q16[k] = 0xFFFFu; continue; }
@@ -260,6 +265,7 @@ void BgenAhead::host_rows(const BlkRef& br, DosPrep& d, int lo) {
         } else q16[k] = (uint16_t)qi;
         tot += v; inf += e; ++ns;
         if (per_trait && has_missing[k]) subtract_masked(Mc, n, P, k, v, e, af_t, ns_t, info_t);
+        if (af_cc && any_case[k]) add_cases(Cc, n, P, k, v, af_case, ns_case);
       }
       for (int64_t k = n; k < ld16; ++k) q16[k] = 0;
       if (!bgen_dosage_integral(worst)) d.host_bad = 1;          // prob0 + prob1 > 1 in the file: not a dosage in [0, 2], the general route reports what the reference would
@@ -288,6 +294,7 @@ void BgenAhead::prepare(size_t gi) {
     if (cm_.coding) d.sum_pos.assign(bs, 0.0);
     d.total.assign(bs, 0.0); d.info_num.assign(bs, 0.0); d.ns1.assign(bs, 0); d.ignored.assign(bs, 0);
     if (cm_.per_trait) { d.af_t.assign((size_t)bs * P, 0.0); d.ns_t.assign((size_t)bs * P, 0); d.info_t.assign((size_t)bs * P, 0.0); }
+    if (cm_.af_cc) { d.af_case.assign((size_t)bs * P, 0.0); d.ns_case.assign((size_t)bs * P, 0); }
     d.w_inf.assign(nt_prep, 0.0); d.w_walk.assign(nt_prep, 0.0);
     // the group's first rows on the device and, beside them, its last blocks on the host threads; a group the decoder turns down goes to
     // the host threads as a whole (a damaged stream, another encoding: their messages are the reference's)

@@ -166,6 +166,81 @@ class Step2QT:
         self._check(self.lib.rg_s2_group_sums_int(self.h, ptr, ld, bs, on_device, sums.ctypes.data))
         return sums
 
+    # ---- allele counts among the cases of each binary trait (rg_s2_set_cases; `--af-cc`) ---------------------------------------------------
+    def set_cases(self, is_case, mask=None) -> None:
+        """is_case [P][n] 0 / 1 (None clears the cases).  mask [P][n]: the trait masks the cases are intersected with; None = those of set_null."""
+        if is_case is None:
+            self._check(self.lib.rg_s2_set_cases(self.h, None, None))
+            return
+        is_case = np.ascontiguousarray(np.asarray(is_case) != 0, dtype=np.uint8)
+        if is_case.shape != (self.P, self.n):
+            raise ValueError("set_cases: is_case must be [P][n]")
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape != (self.P, self.n):
+                raise ValueError("set_cases: mask must be [P][n]")
+            mp = mask.ctypes.data
+        self._check(self.lib.rg_s2_set_cases(self.h, is_case.ctypes.data, mp))
+
+    def case_counts(self, rows, flip: bool = False) -> np.ndarray:
+        """Hard calls as group_counts takes them -> int32 [bs][P][3]: calls equal to 1, equal to 2 and observed among the observed cases of trait p.
+        Additive under every coding.  With a group set too the launch covers both plane sets (the rows are read once): group_counts_last() then
+        returns what group_counts would for the same rows."""
+        on_device = 0
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=np.uint8)
+            bs, ld, ptr = rows.shape[0], rows.shape[1], rows.ctypes.data
+        else:
+            if not (rows.is_cuda and rows.element_size() == 1 and rows.dim() == 2 and rows.stride(1) == 1):
+                raise ValueError("case_counts: device rows must be a 2-d uint8 CUDA tensor with unit byte stride")
+            bs, ld, ptr, on_device = rows.shape[0], rows.stride(0), rows.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(rows.device).synchronize()
+        if rows.shape[1] < (self.n + 3) // 4:
+            raise ValueError("case_counts: rows must hold ceil(n / 4) bytes")
+        counts = np.zeros((bs, self.P, 3), np.int32)
+        self._check(self.lib.rg_s2_case_counts_packed(self.h, ptr, ld, bs, on_device, 1 if flip else 0, counts.ctypes.data))
+        return counts
+
+    def case_sums_int(self, G) -> np.ndarray:
+        """Integer dosages as group_sums_int takes them -> int64 [bs][P][2]: exact sum of the observed values (units of 1 / scale) and observed count
+        among the observed cases of trait p.  group_sums_last() as for case_counts."""
+        on_device = 0
+        if isinstance(G, np.ndarray):
+            G = np.ascontiguousarray(G, dtype=np.uint16)
+            bs, ld, ptr = G.shape[0], G.shape[1], G.ctypes.data
+        else:
+            if not (G.is_cuda and G.element_size() == 2 and G.dim() == 2 and G.stride(1) == 1):
+                raise ValueError("case_sums_int: device G must be a 2-d CUDA tensor of 2-byte elements with unit sample stride")
+            bs, ld, ptr, on_device = G.shape[0], G.stride(0), G.data_ptr(), 1
+            import torch
+            torch.cuda.current_stream(G.device).synchronize()
+        if G.ndim != 2 or G.shape[1] < self.n:
+            raise ValueError("case_sums_int: G must be [bs][>= n]")
+        sums = np.zeros((bs, self.P, 2), np.int64)
+        self._check(self.lib.rg_s2_case_sums_int(self.h, ptr, ld, bs, on_device, sums.ctypes.data))
+        return sums
+
+    def group_counts_last(self, bs: int) -> np.ndarray:
+        """The group's int32 [bs][1 + P][3] of the last case_counts launch (a group must have been set then; bs: that call's number of rows)."""
+        counts = np.zeros((bs, 1 + self.P, 3), np.int32)
+        self._check(self.lib.rg_s2_group_counts_last(self.h, bs, counts.ctypes.data))
+        return counts
+
+    def group_sums_last(self, bs: int) -> np.ndarray:
+        """The group's int64 [bs][1 + P][2] of the last case_sums_int launch (a group must have been set then; bs: that call's number of rows)."""
+        sums = np.zeros((bs, 1 + self.P, 2), np.int64)
+        self._check(self.lib.rg_s2_group_sums_last(self.h, bs, sums.ctypes.data))
+        return sums
+
+    def case_rows_staged(self):
+        """(device address, pitch in elements) of the copy the last case entry made of its HOST rows: what a score entry of the same block takes
+        with rows_on_device / g_on_device = 1 instead of uploading the rows again.  Valid until the next count entry or set call."""
+        ptr, ld = C.c_void_p(), C.c_int64()
+        self._check(self.lib.rg_s2_case_rows_staged(self.h, C.byref(ptr), C.byref(ld)))
+        return ptr.value, ld.value
+
     def score_block(self, G, numtol: float = NUMTOL) -> dict:
         """G: numpy [bs][n] float64 (host), or a CUDA torch tensor [bs][n] float64 (read in place).  Missing = NaN or < 0."""
         on_device = 0

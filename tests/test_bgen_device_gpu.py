@@ -2,7 +2,12 @@
 
 The arbiter of the inflate kernel is zlib itself (python's zlib module = the library the reference calls, Geno.cpp:2200-2210): every inflated byte
 of every stream must be zlib's.  The walk is held to the bytes: integer dosages q = b1 + 2 b0 (units of 1 / 255), the exact integer sums, their
-per-trait parts, and -- through them -- the doubles the host route accumulates in sample order (rg_bgen_read_dosages_info), to 1e-12."""
+per-trait parts (tests/bgen_restate.py), and -- through them -- the doubles the host route accumulates in sample order
+(rg_bgen_read_dosages_info), to 1e-12.
+
+Every stream here comes out of zlib's own compressor.  What that compressor never writes but an inflater must read, the kernels' size, ring and
+framing edges and the refusals built on purpose are in tests/test_bgen_device_edges_gpu.py, on the hand-built streams of tests/deflate_cases.py
+(pinned against zlib without a GPU by tests/test_deflate_cases_cpu.py)."""
 import os
 import zlib
 
@@ -11,36 +16,9 @@ import pytest
 
 from oracle import bgen as obg
 from regenie_amd.bgen import BgenDevice, BgenFile
+from tests.bgen_restate import check as _check, expect as _expect
 
 pytestmark = pytest.mark.gpu
-
-
-def _expect(blocks, n_file, file_idx, ref_first, mask=None):
-    """numpy restatement of the walk over inflated blocks [nvar, 10 + 3 N]."""
-    fi = np.arange(n_file) if file_idx is None else np.asarray(file_idx)
-    miss = (blocks[:, 8:8 + n_file] & 0x80) != 0
-    pr = blocks[:, 10 + n_file:10 + 3 * n_file].reshape(blocks.shape[0], n_file, 2).astype(np.int64)
-    b0, b1 = pr[:, fi, 0], pr[:, fi, 1]
-    ms = miss[:, fi]
-    bx = np.where(b0 + b1 < 255, 255 - b0 - b1, 0) if ref_first else b0
-    q = b1 + 2 * bx
-    inf = 255 * (4 * bx + b1) - q * q
-    obs = ~ms
-    out = {"g16": np.where(ms, 0xFFFF, q).astype(np.uint16), "sum_q": (q * obs).sum(axis=1), "sum_info": (inf * obs).sum(axis=1),
-           "n_obs": obs.sum(axis=1), "max_q": np.where(obs, q, 0).max(axis=1)}
-    if mask is not None:
-        mm = (np.asarray(mask) == 0)                                  # [P, n]: missing for the trait
-        out["sum_q_t"] = np.stack([((q * obs) * mm[p]).sum(axis=1) for p in range(mm.shape[0])], axis=1)
-        out["sum_info_t"] = np.stack([((inf * obs) * mm[p]).sum(axis=1) for p in range(mm.shape[0])], axis=1)
-        out["n_obs_t"] = np.stack([(obs * mm[p]).sum(axis=1) for p in range(mm.shape[0])], axis=1)
-    return out
-
-
-def _check(res, want):
-    assert (res["status"] == 0).all(), res["status"]
-    for k, v in want.items():
-        assert np.array_equal(res[k], v), k
-    assert (res["g16_pad"] == 0).all()
 
 
 @pytest.mark.parametrize("name", ["example.bgen", "example_3chr.bgen"])
@@ -97,7 +75,7 @@ def _write(path, probs, miss, level, strategy=zlib.Z_DEFAULT_STRATEGY, wbits=15)
 
 @pytest.mark.parametrize("level", [1, 6, 9, 0])
 def test_streams_of_every_kind(tmp_path, level):
-    """60,000 samples (blocks of 180 KB: dozens of deflate blocks per stream, matches further back than the 8 KB the kernel keeps in LDS),
+    """60,000 samples (blocks of 180 KB: dozens of deflate blocks per stream, matches further back than the 4 KB the kernel keeps in LDS: RING = 4096),
     hard calls with a share of genuine probabilities and missing samples, long runs (a monomorphic variant: matches of length 258 at distance 2),
     random bytes (literals only, long codes) -- at zlib levels 1 (what tools/bgen_e2e.py writes), 6, 9 and 0 (stored blocks)."""
     rng = np.random.default_rng(10 + level)
